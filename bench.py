@@ -23,8 +23,15 @@ Inputs (scenario pool, env states) are resident in HBM before the timed region.
 Observations stream into a ring of R = 16 device buffers (1.7 GB, 6.6x the
 256 MB Infinity Cache), as a trainer's per-tick feature tensors would.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value,
+ms_per_step, config, the episode summary and the process group's account).  --full adds what
+takes runs of its own: the in-situ write ceiling, the per-launch kernel duration (HIP events
+and the profiler's device records), the roofline block and the cpu_baseline legs.
+--dump-outputs DIR writes what the last timed step gave its caller (last_step_outputs) as
+DIR/<name>.npy.
 
 `--gpus N > 1` without torchrun's environment starts N rank processes itself
 (python -m torch.distributed.run) before touching the GPU.  Rank 0 prints one
@@ -134,6 +141,14 @@ def parse(argv=None):
     p.add_argument("--obs-format", choices=("f32", "bf16", "u8"), default="f32",
                    help="observation element type (the same exact values in each; the metric's "
                         "line is f32, what students/imitation.py:73 feeds the model)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need, each in runs of its "
+                        "own outside the timed region: the write ceiling of the ring, the kernel's "
+                        "duration per launch, the roofline block and the cpu_baseline legs")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step gave its caller as "
+                        "DIR/<name>.npy (float32 / float64; at most 64 MB: observations of a fixed "
+                        "seeded sample of envs)")
     p.add_argument("--traffic", default=None,
                    help="PMC traffic JSON (tools/pmc_summary.py); default profiles/pmc_traffic*.json")
     args = p.parse_args(argv)
@@ -274,6 +289,19 @@ def fill_ceiling(bufs, reps=8):
     return nbytes / (ms * 1e-3) / 1e9, ms * 1e3 / (reps * len(bufs))
 
 
+def warm_ring(bufs, passes=5):
+    """Setup of a plain run: the ring slots filled `passes` times in turn (~3 ms on the card,
+    the same fills fill_ceiling issues, untimed), so that the warmup and the timed steps start
+    on written pages and a busy device whatever --warmup is.  A 20-step run's whole timed region
+    is 0.4 ms and its 5 warmup ticks reach 5 of 16 slots: with one pass instead of five it
+    measured 2 % slower, with none 8 % slower (alternating runs on one card)."""
+    import torch
+    for _ in range(passes):
+        for b in bufs:
+            b.zero_()
+    torch.cuda.synchronize()
+
+
 
 def pmc_traffic(args, workload, k):
     """HBM bytes per launch of this workload's dominant kernel from the PMC passes
@@ -322,6 +350,52 @@ def profiled_kernel_us(fn, m, name):
     except Exception:                               # no device tracer on this build
         return None
 
+
+
+DUMP_OBS_BYTES = 48 << 20     # observation rows dumped (float32); the whole dump stays under 64 MB
+
+
+def sample_rows(n, row_bytes, budget=DUMP_OBS_BYTES, seed=0):
+    """The rows of an [n, ...] output that --dump-outputs keeps: all of them when they fit the
+    budget, else a fixed sorted sample drawn from RandomState(seed) (the same rows every run)."""
+    m = max(1, budget // max(1, row_bytes))
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.RandomState(seed).choice(n, size=m, replace=False)).astype(np.int64)
+
+
+def last_step_outputs(slot, ring, reward, done, success, labels=None):
+    """What the last timed tick gave its caller, as host arrays: the tick's ring slot of every
+    output.  Observations (any obs format holds the same exact values) as float32 rows of the
+    envs sample_rows picks, obs_rows naming them; reward, done, success and the teacher's labels
+    of every env."""
+    import torch
+    n = ring.shape[1]
+    rows = sample_rows(n, ring.shape[2] * 4)
+    idx = torch.as_tensor(rows, device=ring.device)
+    out = {"obs": ring[slot].index_select(0, idx).to(torch.float32).cpu().numpy(),
+           "obs_rows": rows.astype(np.float64),
+           "reward": reward[slot].cpu().numpy().astype(np.float32),
+           "done": done[slot].cpu().numpy().astype(np.float32),
+           "success": success[slot].cpu().numpy().astype(np.float32)}
+    if labels is not None:
+        out["labels"] = labels[slot].cpu().numpy().astype(np.float32)
+    return out
+
+
+def dump_outputs(dirname, arrays, rank=0, world_size=1):
+    """DIR/<name>.npy per array (float32 / float64); with more than one rank each rank writes
+    its own shard as <name>.rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        total += a.nbytes
+        suffix = f".rank{rank}" if world_size > 1 else ""
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
 
 
 def _init_ranks(args):
@@ -421,8 +495,11 @@ def run(args):
             tick += k
 
     # the in-situ write ceiling of the same ring, slot by slot (before the warmup, so that the
-    # timed region follows the kernel's own warm launches)
-    ceiling_gbs, ceiling_slot_us = fill_ceiling([ring[r] for r in range(R)], reps=4)
+    # timed region follows the kernel's own warm launches); --full only
+    if args.full:
+        ceiling_gbs, ceiling_slot_us = fill_ceiling([ring[r] for r in range(R)], reps=4)
+    else:
+        warm_ring([ring[r] for r in range(R)])
     for k in warm_plan:
         launch(k)
     sim.check()
@@ -444,23 +521,31 @@ def run(args):
     elapsed = D.max_over_ranks(t1 - t0, dev)
     local_s = t1 - t0
 
+    # ---- --dump-outputs: the last timed tick's slot of every output ring, copied out before
+    # anything else is launched ---------------------------------------------------------------
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs,
+                     last_step_outputs((tick - 1) % R, ring, reward, done, success,
+                                       labels if teacher else None), rank, world_size)
+
     # ---- per-launch kernel duration, HIP events on the launch stream (outside the timed
     # region): m back-to-back launches of k_eff ticks (as many as the timed region had, at
-    # least 8) between one pair of events, so no event sits between two launches -------------
-    kstream = torch.cuda.current_stream(dev)
-    m = min(max(len(timed_plan), 8), 200)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    ev0.record(kstream)
-    for _ in range(m):
-        launch(k_eff)
-    ev1.record(kstream)
-    torch.cuda.synchronize()
-    kernel_ms = ev0.elapsed_time(ev1) / m                                # per launch (k_eff ticks)
+    # least 8) between one pair of events, so no event sits between two launches; --full only
+    kernel_ms = prof_us = None
+    if args.full:
+        kstream = torch.cuda.current_stream(dev)
+        m = min(max(len(timed_plan), 8), 200)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        ev0.record(kstream)
+        for _ in range(m):
+            launch(k_eff)
+        ev1.record(kstream)
+        torch.cuda.synchronize()
+        kernel_ms = ev0.elapsed_time(ev1) / m                            # per launch (k_eff ticks)
     # one launch per tick (craft_step / craft_step_teach): price the kernel's own duration (the
     # profiler's device records, as rocprof reports them), not launches plus dispatch gaps
-    prof_us = None
-    if K == 1 and not args.no_kernel_profiler:
+    if args.full and K == 1 and not args.no_kernel_profiler:
         if teacher and args.teacher_mode == "fused":
             pname = sim.step_shape(teach=True)[0]
         else:
@@ -504,8 +589,6 @@ def run(args):
             if teacher and args.teacher_mode != "fused":
                 kname += " + teacher_kernel"
             shape = {"tile": kenvs, "kernel": kn, "teacher_lanes": lanes}
-        kernel_us_priced = prof_us if prof_us is not None else kernel_ms * 1e3
-        achieved = bps * n * k_eff / (kernel_us_priced * 1e-6) / 1e9
         workload = f"{args.world}_w{win}_B{n}_" + (
             "teacher_labels_full_features" if teacher else "random_rollout_full_features")
         if K > 1:
@@ -516,16 +599,6 @@ def run(args):
             workload += "_" + args.teacher_mode
             if args.teacher_actions != "policy":
                 workload += "_" + ("label_actions" if args.teacher_actions == "label" else "bc_mix")
-        traffic = pmc_traffic(args, workload, k_eff)
-        if teacher and K > 1:
-            bound = "hbm (the teacher's walk and BFS run in the interval's slack beside the stream)"
-        elif teacher:
-            bound = ("latency: the tick's prologue plus the BFS beside the observation stream "
-                     "(store floor of the tick's bytes at the in-situ ceiling below)")
-        elif K == 1:
-            bound = "hbm (one launch per tick: plus the tick's latency-bound prologue)"
-        else:
-            bound = "hbm"
         line = {
             "metric": "env-steps/sec (whole node), 12x12 craft_medium, batch=65536",
             "value": value,
@@ -550,36 +623,50 @@ def run(args):
                             "max_timesteps": sim.config.max_timesteps, "ticks_per_launch": K,
                             "launches": len(timed_plan), "teach_table": args.teach_table,
                             "obs_store": ["write-back", "nontemporal", "sc1"][obs_store]}, **shape),
-            "roofline": {"bound": bound, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kname,
-                         "kernel_us": kernel_us_priced,
-                         "kernel_us_source": "torch profiler device records (as rocprof)" if prof_us
-                         is not None else "HIP events over back-to-back launches",
-                         "kernel_us_events": kernel_ms * 1e3, "ticks_per_launch": k_eff,
-                         "bytes_per_launch": bps * n * k_eff, "bytes_per_env_step": bps,
-                         "ceiling_gbs": ceiling_gbs, "frac_of_ceiling": achieved / ceiling_gbs,
-                         **hbm_rate(traffic, kernel_us_priced),
-                         "ceiling": f"torch zero_ of each {R}-slot ring buffer in turn "
-                                    f"({ceiling_slot_us:.1f} us per {ring[0].numel() * ring.element_size() / 1e6:.0f} MB "
-                                    "slot), measured in this run before the timed region"},
             "episodes": {"successes": stats[0], "episodes": stats[1], "env_steps": stats[2]},
             "dist": report,
         }
-        if world_size == 1 and not args.no_cpu_baseline:
-            c_leg = cpu_baseline_c(sim.config, grids, specs, env_base, args.seed, args.cpu_seconds,
-                                   teacher=teacher)
-            if teacher:                     # the numpy restatement has no teacher: no like-for-like leg
-                np_leg = None
+        if args.full:
+            kernel_us_priced = prof_us if prof_us is not None else kernel_ms * 1e3
+            achieved = bps * n * k_eff / (kernel_us_priced * 1e-6) / 1e9
+            traffic = pmc_traffic(args, workload, k_eff)
+            if teacher and K > 1:
+                bound = "hbm (the teacher's walk and BFS run in the interval's slack beside the stream)"
+            elif teacher:
+                bound = ("latency: the tick's prologue plus the BFS beside the observation stream "
+                         "(store floor of the tick's bytes at the in-situ ceiling below)")
+            elif K == 1:
+                bound = "hbm (one launch per tick: plus the tick's latency-bound prologue)"
             else:
-                try:
-                    np_leg = cpu_baseline_numpy(sim.config, grids, specs, env_base, args.seed,
-                                                args.cpu_seconds)
-                except Exception as e:      # the C leg stands alone if process pools are refused
-                    np_leg = {"error": f"{type(e).__name__}: {e}"}
-            if teacher and args.teacher_actions != "policy":
-                c_leg["note"] = ("the C leg acts on the hashed policy, not on the labels: the same "
-                                 "step, features and teacher work per env-step")
-            line["cpu_baseline"] = dict(c_leg, **({"python_numpy": np_leg} if np_leg is not None else {}))
+                bound = "hbm"
+            line["roofline"] = {
+                "bound": bound, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kname,
+                "kernel_us": kernel_us_priced,
+                "kernel_us_source": "torch profiler device records (as rocprof)" if prof_us
+                is not None else "HIP events over back-to-back launches",
+                "kernel_us_events": kernel_ms * 1e3, "ticks_per_launch": k_eff,
+                "bytes_per_launch": bps * n * k_eff, "bytes_per_env_step": bps,
+                "ceiling_gbs": ceiling_gbs, "frac_of_ceiling": achieved / ceiling_gbs,
+                **hbm_rate(traffic, kernel_us_priced),
+                "ceiling": f"torch zero_ of each {R}-slot ring buffer in turn "
+                           f"({ceiling_slot_us:.1f} us per {ring[0].numel() * ring.element_size() / 1e6:.0f} MB "
+                           "slot), measured in this run before the timed region"}
+            if world_size == 1 and not args.no_cpu_baseline:
+                c_leg = cpu_baseline_c(sim.config, grids, specs, env_base, args.seed, args.cpu_seconds,
+                                       teacher=teacher)
+                if teacher:                     # the numpy restatement has no teacher: no like-for-like leg
+                    np_leg = None
+                else:
+                    try:
+                        np_leg = cpu_baseline_numpy(sim.config, grids, specs, env_base, args.seed,
+                                                    args.cpu_seconds)
+                    except Exception as e:      # the C leg stands alone if process pools are refused
+                        np_leg = {"error": f"{type(e).__name__}: {e}"}
+                if teacher and args.teacher_actions != "policy":
+                    c_leg["note"] = ("the C leg acts on the hashed policy, not on the labels: the same "
+                                     "step, features and teacher work per env-step")
+                line["cpu_baseline"] = dict(c_leg, **({"python_numpy": np_leg} if np_leg is not None else {}))
         print(json.dumps(line), flush=True)
     D.shutdown()
 
@@ -680,9 +767,10 @@ def run_trainer(args):
     for _ in range(args.warmup):
         rollout()
     sim.check()
-    ceil_buf = sim.empty_obs()          # do_rollout rewrites one observation buffer every tick
-    ceiling_gbs, ceiling_us = fill_ceiling([ceil_buf], reps=16)
-    del ceil_buf
+    if args.full:
+        ceil_buf = sim.empty_obs()      # do_rollout rewrites one observation buffer every tick
+        ceiling_gbs, ceiling_us = fill_ceiling([ceil_buf], reps=16)
+        del ceil_buf
     D.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -700,9 +788,20 @@ def run_trainer(args):
                           names=("slot_env_ticks", "live_env_steps", "ticks"))
     tot = D.reduce_episode_stats(torch.as_tensor(local, dtype=torch.int64, device=dev)).cpu().tolist()
 
-    # ---- per-tick split, outside the timed region: HIP events at the start and the end of the
-    # student's kernels of every tick of one more rollout; the env launch (craft_step_teach)
-    # runs between one tick's policy end and the next one's start ----
+    # ---- --dump-outputs: the last timed rollout's info (its arrays) and the labels its last
+    # tick handed to receive() ----------------------------------------------------------------
+    if args.dump_outputs:
+        out = {"action_seqs": info.action_seqs, "n_actions": info.n_actions,
+               "success": info.success, "distances": info.distances, "is_get": info.is_get}
+        if received:
+            out["last_labels"] = received[-1]
+        out = {k: torch.as_tensor(v).cpu().numpy().astype(np.float32) for k, v in out.items()}
+        out["counts"] = np.asarray([info.ticks, info.num_interactions, info.num_steps], dtype=np.float64)
+        dump_outputs(args.dump_outputs, out, rank, world_size)
+
+    # ---- per-tick split, outside the timed region (--full only): HIP events at the start and
+    # the end of the student's kernels of every tick of one more rollout; the env launch
+    # (craft_step_teach) runs between one tick's policy end and the next one's start ----
     marks = []
 
     def timed_act(obs, t):
@@ -713,29 +812,29 @@ def run_trainer(args):
         marks.append((a, b))
         return out
 
-    torch.cuda.synchronize()
-    w0 = time.perf_counter()
-    info = do_rollout(sim, spec_d, timed_act, False, behavior_clone=bc_d, receive=receive,
-                      lookahead=fused, fused_teacher=fused)
-    torch.cuda.synchronize()
-    wall = (time.perf_counter() - w0) / max(1, info.ticks)
-    pol_us = float(np.mean([a.elapsed_time(b) for a, b in marks[:info.ticks]])) * 1e3
-    env_us = float(np.mean([marks[k][1].elapsed_time(marks[k + 1][0])
-                            for k in range(min(info.ticks, len(marks) - 1))])) * 1e3
-    sim.check()
-    # the tick kernel's own device duration over one more rollout (as rocprof prices it: without
-    # the dispatch gaps env_kernel above includes)
-    kname, kenvs, lanes = sim.step_shape(teach=fused)
-    prof_us = None if args.no_kernel_profiler else profiled_kernel_us(
-        lambda: do_rollout(sim, spec_d, act, False, behavior_clone=bc_d, receive=receive,
-                           lookahead=fused, fused_teacher=fused), 1, kname)
-    kernel_us = prof_us if prof_us else env_us
+    if args.full:
+        torch.cuda.synchronize()
+        w0 = time.perf_counter()
+        info = do_rollout(sim, spec_d, timed_act, False, behavior_clone=bc_d, receive=receive,
+                          lookahead=fused, fused_teacher=fused)
+        torch.cuda.synchronize()
+        wall = (time.perf_counter() - w0) / max(1, info.ticks)
+        pol_us = float(np.mean([a.elapsed_time(b) for a, b in marks[:info.ticks]])) * 1e3
+        env_us = float(np.mean([marks[k][1].elapsed_time(marks[k + 1][0])
+                                for k in range(min(info.ticks, len(marks) - 1))])) * 1e3
+        sim.check()
+        # the tick kernel's own device duration over one more rollout (as rocprof prices it:
+        # without the dispatch gaps env_kernel above includes)
+        kname, kenvs, lanes = sim.step_shape(teach=fused)
+        prof_us = None if args.no_kernel_profiler else profiled_kernel_us(
+            lambda: do_rollout(sim, spec_d, act, False, behavior_clone=bc_d, receive=receive,
+                               lookahead=fused, fused_teacher=fused), 1, kname)
+        kernel_us = prof_us if prof_us else env_us
 
     if rank == 0:
         win = sim.params["WINDOW_WIDTH"]
         F = sim.n_features
         bps = bytes_per_env_step(sim.width, sim.height, win, F, True, 4)
-        achieved = bps * n / (kernel_us * 1e-6) / 1e9
         workload = f"{args.world}_w{win}_B{n}_trainer_closed_loop_train_{args.trainer_teacher}_teacher"
         value = tot[1] / elapsed                     # live env-steps (num_interactions)
         line = {
@@ -764,35 +863,39 @@ def run_trainer(args):
                        "parallelism": f"env-shard x{world_size}"},
             "slot_env_steps_per_s": tot[0] / elapsed,
             "dist": report,
-            "per_tick_us": {"timed_wall": elapsed * 1e6 / max(1, tot[2] // world_size),
-                            "eager_wall": wall * 1e6, "policy": pol_us, "env": env_us,
-                            "env_kernel_device": kernel_us,
-                            "host_gap": wall * 1e6 - pol_us - env_us,
-                            "note": "timed_wall: the timed region per tick; the rest from one "
-                                    "instrumented eager (lookahead, no graph) rollout after it: "
-                                    "HIP events at the start and end of the student's kernels; "
-                                    "env = policy end to the next tick's policy start (the "
-                                    "craft_step_teach launch, its any-live flag stored into mapped "
-                                    "host memory, and the dispatch gaps around it); "
-                                    "env_kernel_device = the kernel's own duration"},
-            "roofline": {"bound": "latency (tick prologue + BFS beside the observation stream)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(args, workload, 1),
-                         **hbm_rate(pmc_traffic(args, workload, 1), kernel_us),
-                         "kernel": (f"{kname} (craft_step_teach, {kenvs} envs, {lanes} teacher lanes)" if fused
-                                    else f"{kname} (craft_step_ex, {kenvs} envs; craft_teacher beside act())"),
-                         "kernel_us": kernel_us,
-                         "kernel_us_source": ("torch profiler device records (as rocprof)" if prof_us
-                                              else "HIP events: policy end to next policy start"),
-                         "bytes_per_env_step": bps,
-                         "bytes_per_launch": bps * n, "ceiling_gbs": ceiling_gbs,
-                         "frac_of_ceiling": achieved / ceiling_gbs,
-                         "ceiling": f"torch zero_ of one [n, F] fp32 buffer rewritten in place, as "
-                                    f"do_rollout's observation buffer is ({ceiling_us:.1f} us per fill)"},
+            "per_tick_us": {"timed_wall": elapsed * 1e6 / max(1, tot[2] // world_size)},
         }
-        if world_size == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline_trainer(sim.config, grids, specs, W, bias, bc,
-                                                        args.cpu_seconds)
+        if args.full:
+            achieved = bps * n / (kernel_us * 1e-6) / 1e9
+            line["per_tick_us"].update({
+                "eager_wall": wall * 1e6, "policy": pol_us, "env": env_us,
+                "env_kernel_device": kernel_us,
+                "host_gap": wall * 1e6 - pol_us - env_us,
+                "note": "timed_wall: the timed region per tick; the rest from one "
+                        "instrumented eager (lookahead, no graph) rollout after it: "
+                        "HIP events at the start and end of the student's kernels; "
+                        "env = policy end to the next tick's policy start (the "
+                        "craft_step_teach launch, its any-live flag stored into mapped "
+                        "host memory, and the dispatch gaps around it); "
+                        "env_kernel_device = the kernel's own duration"})
+            line["roofline"] = {
+                "bound": "latency (tick prologue + BFS beside the observation stream)",
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(args, workload, 1),
+                **hbm_rate(pmc_traffic(args, workload, 1), kernel_us),
+                "kernel": (f"{kname} (craft_step_teach, {kenvs} envs, {lanes} teacher lanes)" if fused
+                           else f"{kname} (craft_step_ex, {kenvs} envs; craft_teacher beside act())"),
+                "kernel_us": kernel_us,
+                "kernel_us_source": ("torch profiler device records (as rocprof)" if prof_us
+                                     else "HIP events: policy end to next policy start"),
+                "bytes_per_env_step": bps,
+                "bytes_per_launch": bps * n, "ceiling_gbs": ceiling_gbs,
+                "frac_of_ceiling": achieved / ceiling_gbs,
+                "ceiling": f"torch zero_ of one [n, F] fp32 buffer rewritten in place, as "
+                           f"do_rollout's observation buffer is ({ceiling_us:.1f} us per fill)"}
+            if world_size == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline_trainer(sim.config, grids, specs, W, bias, bc,
+                                                            args.cpu_seconds)
         print(json.dumps(line), flush=True)
     D.shutdown()
 

@@ -39,6 +39,36 @@ def test_driver_command_line_parses():
     assert bench.plan_launches(a.warmup, a.ticks_per_launch) == [5]
 
 
+def test_full_and_dump_outputs_arguments():
+    """A plain run is the default; --full and --dump-outputs DIR are opt-in."""
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "out" and a.steps == 7
+
+
+def test_sample_rows_fixed_and_within_budget():
+    """--dump-outputs keeps every row of an output that fits and otherwise the same sorted
+    seeded sample on every call; the headline shape's sample stays under the 64 MB limit."""
+    import numpy as np
+    assert bench.sample_rows(100, 1616).tolist() == list(range(100))
+    a, b = bench.sample_rows(65536, 1616), bench.sample_rows(65536, 1616)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_OBS_BYTES // 1616
+    assert (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < 65536
+    assert len(a) * 1616 + 5 * 65536 * 8 < 64 << 20      # obs + rows, reward, done, success, labels
+
+
+def test_dump_outputs_writes_float_npy(tmp_path):
+    import numpy as np
+    arrays = {"obs": np.arange(6, dtype=np.float32).reshape(2, 3), "done": np.array([0, 1], dtype=np.uint8)}
+    bench.dump_outputs(str(tmp_path / "d"), arrays)
+    obs, done = np.load(tmp_path / "d" / "obs.npy"), np.load(tmp_path / "d" / "done.npy")
+    assert obs.dtype == np.float32 and np.array_equal(obs, arrays["obs"])
+    assert done.dtype == np.float64 and done.tolist() == [0.0, 1.0]
+    bench.dump_outputs(str(tmp_path / "d"), arrays, rank=1, world_size=2)
+    assert (tmp_path / "d" / "obs.rank1.npy").exists()
+
+
 @pytest.mark.parametrize("argv", [["--steps", "0"], ["--gpus", "0"], ["--warmup", "-1"],
                                   ["--ticks-per-launch", "0"], ["--tile", "48"]])
 def test_parse_rejects_before_gpu_work(argv):

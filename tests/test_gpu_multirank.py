@@ -21,7 +21,7 @@ def _bench(*args, timeout=240):
     env.pop("WORLD_SIZE", None)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5",
-                          "--no-cpu-baseline", *args], cwd=REPO, env=env, capture_output=True,
+                          "--full", "--no-cpu-baseline", *args], cwd=REPO, env=env, capture_output=True,
                          text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -205,14 +205,18 @@ def test_dataset_flatten_and_batches(golden):
         Dataset(bad, "dev", tm)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/data"), reason="reference split files absent")
-def test_dataset_reads_reference_split_files(golden):
-    """The committed split JSON files themselves (build container only)."""
+def test_dataset_reads_reference_split_files(golden, tmp_path):
+    """The reference's split JSON files themselves (tests/golden/craft_medium_{split}.json.gz:
+    the files byte for byte, gzipped), read from a path as a trainer reads them."""
+    import gzip
     from psketch_amd.dataset import Dataset
     fx = golden("devtest.npz")
     _, _, tm, _ = make_tables("craft_medium")
     for split in ["dev", "test"]:
-        ds = Dataset(f"/root/reference/data/craft_medium_{split}.json", split, tm)
+        path = tmp_path / f"craft_medium_{split}.json"
+        with gzip.open(os.path.join(REPO, "tests", "golden", path.name + ".gz"), "rb") as f:
+            path.write_bytes(f.read())
+        ds = Dataset(str(path), split, tm)
         spec = np.stack(Dataset.specs(list(ds)), axis=1)
         assert np.array_equal(spec[:, 1:3], fx[f"{split}_pos"])
         assert np.array_equal(spec[:, 4], fx[f"{split}_task"])

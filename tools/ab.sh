@@ -13,7 +13,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for spec in ${SPECS}; do
     name=${spec%%=*}; rest=${spec#*=}; envs=${rest%%|*}; args=${rest#*|}
     for steps in ${STEPS:-20 512}; do
-      env ${envs//,/ } timeout -k 10 120 python bench.py --steps $steps --warmup 5 --no-cpu-baseline ${args//,/ } ${BENCH_ARGS:-} > "$OUT/$name.$steps.$rep.json" 2> "$OUT/$name.$steps.$rep.err"
+      env ${envs//,/ } timeout -k 10 120 python bench.py --full --steps $steps --warmup 5 --no-cpu-baseline ${args//,/ } ${BENCH_ARGS:-} > "$OUT/$name.$steps.$rep.json" 2> "$OUT/$name.$steps.$rep.err"
       rc=$?; [ $rc -eq 0 ] || { echo "rc=$rc $name $steps"; tail -3 "$OUT/$name.$steps.$rep.err"; exit $rc; }
       python -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(sys.argv[2], 'steps', sys.argv[3], 'value %.3fG' % (d['value']/1e9), 'kernel_us %.1f' % r['kernel_us'], 'frac %.3f' % r['frac'], r['kernel'])" "$OUT/$name.$steps.$rep.json" "$name" $steps
     done

@@ -13,7 +13,7 @@ cd "$REPO"
 CS=${CPU_SECONDS:-3}
 run() {
   name=$1; shift
-  timeout -k 10 300 python bench.py "$@" --cpu-seconds $CS > "$OUT/$name.json" 2> "$OUT/$name.err"
+  timeout -k 10 300 python bench.py --full "$@" --cpu-seconds $CS > "$OUT/$name.json" 2> "$OUT/$name.err"
   rc=$?; echo "$name rc=$rc"; [ $rc -eq 0 ] || { tail -3 "$OUT/$name.err"; exit $rc; }
 }
 run driver --steps 20 --warmup 5
