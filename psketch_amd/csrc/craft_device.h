@@ -478,13 +478,29 @@ __device__ __forceinline__ void transition(const SimView& v, const uint32_t* rc,
 }
 
 // CraftState.satisfies (craft.py:285-294): 1/0, -1 for None.  `tt` is the
-// task-table entry goal | arg<<4.
+// task-table entry goal | arg<<4.  The one decode; callers differ in where the two things it
+// reads live: have(kind) = the inventory count of a kind, facing() = the kind the agent faces.
+template <class HaveFn, class FacingFn>
+__device__ __forceinline__ int satisfies_with(uint32_t tt, HaveFn have, FacingFn facing) {
+  const int goal = tt & 0xf, arg = (tt >> 4) & 0xff;
+  if (goal == CRAFT_GOAL_GET || goal == CRAFT_GOAL_MAKE) return have(arg) > 0;
+  if (goal == CRAFT_GOAL_GO) return facing() == arg;
+  return -1;
+}
+
+// On a grid row that already has this episode's clears and an inventory row of bytes.
 __device__ __forceinline__ int satisfies(const SimView& v, const uint8_t* g, const uint8_t* iv,
                                          const Agent& s, uint32_t tt) {
-  const int goal = tt & 0xf, arg = (tt >> 4) & 0xff;
-  if (goal == CRAFT_GOAL_GET || goal == CRAFT_GOAL_MAKE) return iv[arg] > 0;
-  if (goal == CRAFT_GOAL_GO) return g[(s.x + dir_dx(s.dir)) * v.H + (s.y + dir_dy(s.dir))] == arg;
-  return -1;
+  return satisfies_with(
+      tt, [&](int arg) __attribute__((always_inline)) { return (int)iv[arg]; },
+      [&]() __attribute__((always_inline)) {
+        return (int)g[(s.x + dir_dx(s.dir)) * v.H + (s.y + dir_dy(s.dir))];
+      });
+}
+
+// Bytes per observation element of a craft_obs_format_t.
+__host__ __device__ constexpr int obs_elem_bytes(int fmt) {
+  return fmt == CRAFT_OBS_F32 ? 4 : (fmt == CRAFT_OBS_BF16 ? 2 : 1);
 }
 
 }  // namespace craft

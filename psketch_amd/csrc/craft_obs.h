@@ -36,7 +36,7 @@ __device__ __forceinline__ obs_vec pack16(const uint8_t* s_obs, int sidx) {
 template <int FMT, int NTHR = kThreads, bool ZERO = false, int U = 4>
 __device__ __forceinline__ void stream_obs(uint8_t* s_obs, void* obs, int64_t env0, int F, int nE,
                                            int policy, int tid) {
-  constexpr int ESZ = FMT == CRAFT_OBS_F32 ? 4 : (FMT == CRAFT_OBS_BF16 ? 2 : 1);
+  constexpr int ESZ = obs_elem_bytes(FMT);
   constexpr int PER = 16 / ESZ;                // values per 16-byte store
   const int total = nE * F;
   const int nv = total / PER;
@@ -49,13 +49,8 @@ __device__ __forceinline__ void stream_obs(uint8_t* s_obs, void* obs, int64_t en
     for (int u = 0; u < U; ++u) {
       const int sidx = base + u * NTHR;
       if (sidx < nv) {
-#ifdef CRAFT_ABL_NOLDS
-        o[u] = obs_vec{(unsigned)sidx, 0u, 0u, 0u};
-        if (false) {
-#else
         o[u] = pack16<FMT>(s_obs, sidx);
         if (ZERO) {
-#endif
           if (FMT == CRAFT_OBS_F32) reinterpret_cast<uint32_t*>(s_obs)[sidx] = 0u;
           else if (FMT == CRAFT_OBS_BF16) reinterpret_cast<uint2*>(s_obs)[sidx] = make_uint2(0u, 0u);
           else reinterpret_cast<uint4*>(s_obs)[sidx] = make_uint4(0u, 0u, 0u, 0u);

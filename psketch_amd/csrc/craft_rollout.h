@@ -31,6 +31,7 @@
 // over a ring of R buffers would.  Used where actions do not depend on the
 // observations (random rollouts, configs 2 and 4; or replayed action tables).
 #pragma once
+#include "craft_episode.h"
 #include "craft_obs.h"
 #include "craft_rollout_split.h"
 
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_kernel(SimView v, RolloutArgs
   const int64_t n = v.n_envs;
   const bool want_obs = a.obs != nullptr;
   const int F = v.F;
-  constexpr int esz = FMT == CRAFT_OBS_F32 ? 4 : (FMT == CRAFT_OBS_BF16 ? 2 : 1);
+  constexpr int esz = obs_elem_bytes(FMT);
   const int n_tiles = (int)((n + TILE - 1) / TILE);
   const int n_chunks = (a.n_ticks + a.chunk - 1) / a.chunk;
   const uint32_t n_units = (uint32_t)n_tiles * (uint32_t)n_chunks;
@@ -103,9 +104,8 @@ __global__ __launch_bounds__(NT, WPE) void rollout_kernel(SimView v, RolloutArgs
   uint64_t st = 0;
   uint32_t init_word = 0;
   uint32_t task_word = 0;                                   // s_task[task]: fixed for the env
-  // cells cleared this episode, so that a restart restores only those from the pristine row:
-  // up to 3 cell ids (bits 0-23), their count (bits 24-25), bit 31 = more (restore the row)
-  uint32_t clr = 0;
+  // cells cleared this episode, so that a restart restores only those from the pristine row
+  ClearList clr;
   bool live = false;
   int64_t slot = 0;
   uint8_t* g = s_grid + tid * v.GS;
@@ -124,98 +124,37 @@ __global__ __launch_bounds__(NT, WPE) void rollout_kernel(SimView v, RolloutArgs
     unsigned long long tc1 = tc0;
     s = unpack_state(st);
     if (live) {
-      int act;
-      if (GIVEN) {
-        act = a.actions[(int64_t)k * n + slot];
-      } else {
-        const uint64_t gid = (uint64_t)(v.env_base + slot);
-#ifdef CRAFT_ABL_NOHASH
-        act = (int)((gid + (uint64_t)tick) % 6u);
-#else
-        act = (int)((uint32_t)(splitmix64(a.seed ^ (gid << 20) ^ (uint64_t)tick) >> 32) % 6u);
-#endif
-      }
+      const int act = GIVEN ? a.actions[(int64_t)k * n + slot] : hashed_action(v, a.seed, slot, tick);
       bool restart = false;
-      if (s.frozen) {
-        d = 1;
-      } else {
-        counted = 1;
-        s.timer -= 1;
-        d = (act == CRAFT_STOP) || s.timer <= 0;
-        restart = d && (a.flags & CRAFT_STEP_AUTORESET);
-      }
-#ifdef CRAFT_ABL_NOSAT
-      if (false) {
-#else
-      if (d) {
-#endif
-        // satisfies() of the pre-step state (the LDS row already has this episode's clears)
-        const int goal = task_word & 0xf, arg = (task_word >> 4) & 0xff;
-        const int fc = (s.x + dir_dx(s.dir)) * v.H + (s.y + dir_dy(s.dir));
-        if (goal == CRAFT_GOAL_GET || goal == CRAFT_GOAL_MAKE) succ = iv[arg] > 0;
-        else if (goal == CRAFT_GOAL_GO) succ = (int)g[fc] == arg;
-        else succ = -1;
-      }
-      if (restart) {                                    // CraftScenario.init, craft.py:268-273
-        s.x = init_word & 0xff; s.y = (init_word >> 8) & 0xff; s.dir = (init_word >> 16) & 3;
-        s.timer = v.maxT;
+      protocol_step(s, act, a.flags, d, counted, restart);
+      // satisfies() of the pre-step state (the LDS row already has this episode's clears)
+      if (d) succ = satisfies(v, g, iv, s, task_word);
+      if (restart) {
+        restart_agent(s, init_word, v.maxT);
 #pragma unroll
         for (int w = 0; w < 8; ++w) ivw[w] = 0u;
-        if (clr >> 31) {
-          // more than 3 cells cleared: the whole scenario row, 12 dword reads in flight at a time
-          for (int q0 = 0; q0 < (v.CS >> 2); q0 += 12) {
-            uint32_t w[12];
-#pragma unroll
-            for (int j = 0; j < 12; ++j) w[j] = q0 + j < (v.CS >> 2) ? pw[q0 + j] : 0u;
-#pragma unroll
-            for (int j = 0; j < 12; ++j)
-              if (q0 + j < (v.CS >> 2)) gw[q0 + j] = w[j];
-          }
-        } else {
-          const uint8_t* pr = reinterpret_cast<const uint8_t*>(pw);
-          const int nc = (clr >> 24) & 3;
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-            if (i < nc) {
-              const int c = (clr >> (8 * i)) & 0xff;
-              g[c] = pr[c];
-            }
-        }
-        clr = 0;
+        clr.restore(g, pw, v.CS);
+        clr.clear();
       } else if (d && !s.frozen) {
-        s.frozen = 1;
-        s.timer = max(s.timer, 0);
+        freeze_agent(s);
       }
       tc1 = CRAFT_NOW();
       if (!d) {
         bool inv_changed = false, mask_changed = false;
         uint32_t m_unused[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the LDS row is the record
-        const int fc = (s.x + dir_dx(s.dir)) * v.H + (s.y + dir_dy(s.dir));   // what USE clears
-#ifndef CRAFT_ABL_NOTRANS
+        const int fc = facing_cell(s, v.H);                // what USE clears
         if (act < 0 || act >= CRAFT_N_ACTIONS) latch_error(v.err, CRAFT_EBADACTION, slot);
         else transition<true>(v, s_rc, g, iv, s, m_unused, act, inv_changed, mask_changed, rcv, slot);
-#endif
-        if (mask_changed) {
-          const uint32_t nc = (clr >> 24) & 3;
-          clr = nc < 3 ? ((clr & 0x00ffffffu) | ((uint32_t)fc << (8 * nc)) | ((nc + 1) << 24)) : (1u << 31);
-        }
+        if (mask_changed) clr.push(fc);
       }
       const unsigned long long tc2 = CRAFT_NOW();
       PACC_C(4, tc1 - tc0);
       PACC_C(5, tc2 - tc1);
       st = pack_state(s);
-      const int64_t o = r * n + slot;
-      if (a.done) a.done[o] = (uint8_t)d;
-      if (a.sat) a.sat[o] = (int8_t)succ;
-      if (a.reward) a.reward[o] = (counted && d && succ == 1) ? 1.0f : 0.0f;
+      store_outputs(a, r * n + slot, d, succ, counted);
     }
-    const uint64_t bs = __ballot(live && counted && d && succ == 1);
-    const uint64_t be = __ballot(live && counted && d);
-    const uint64_t bt = __ballot(live && counted);
-    n_succ += (uint32_t)__popcll(bs);
-    n_end += (uint32_t)__popcll(be);
-    n_step += (uint32_t)__popcll(bt);
-    return live ? ((uint32_t)s.x | ((uint32_t)s.y << 8) | ((uint32_t)s.dir << 16) | (1u << 24)) : 0u;
+    tally_stats(live, counted, d, succ, n_succ, n_end, n_step);
+    return agent_word(s, live);
   };
 
   // ---- D: the whole producer wave scatters the tile's rows into buffer `buf` ------------------
@@ -228,9 +167,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_kernel(SimView v, RolloutArgs
       ag = (uint32_t)__shfl((int)ag, tid % TILE, 64);
     }
     const int e = tid % TILE;
-#ifndef CRAFT_ABL_NOD
     if (ag) scatter_env_part<WIN, P>(v, s_grid + e * v.GS, s_inv + e * kInvStride, ag, buf + e * F, tid / TILE);
-#endif
   };
 
   // ---- once per workgroup: static tables, cleared observation rows ------------------------------
@@ -284,42 +221,16 @@ __global__ __launch_bounds__(NT, WPE) void rollout_kernel(SimView v, RolloutArgs
           m[0] = m0.x; m[1] = m0.y; m[2] = m0.z; m[3] = m0.w;
           m[4] = m1.x; m[5] = m1.y; m[6] = m1.z; m[7] = m1.w;
           s = unpack_state(st);
-          if (s.x < 1 || s.x > v.W - 2 || s.y < 1 || s.y > v.H - 2 || s.scen >= v.pool_count) {
+          if (!state_in_range(v, s)) {
             latch_error(v.err, CRAFT_EINVAL, slot);     // never initialised by reset / set_state
             live = false;
           }
         }
         if (live) {
           task_word = s_task[s.task];
-          // pool[scenario] (L2-resident) -> the pristine row and the grid row, 4 x 16 B in flight
-          const uint4* src = reinterpret_cast<const uint4*>(v.pool + (size_t)s.scen * v.CS);
-          const int nchunk = v.CS >> 4;
-          for (int q0 = 0; q0 < nchunk; q0 += 4) {
-            uint4 cq[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              if (q0 + j < nchunk) cq[j] = src[q0 + j];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              if (q0 + j < nchunk) {
-                const int q = 4 * (q0 + j);
-                pw[q + 0] = gw[q + 0] = cq[j].x; pw[q + 1] = gw[q + 1] = cq[j].y;
-                pw[q + 2] = gw[q + 2] = cq[j].z; pw[q + 3] = gw[q + 3] = cq[j].w;
-              }
-          }
-          clr = 0;
-#pragma unroll
-          for (int w = 0; w < 8; ++w) {                 // cells cleared this episode
-            uint32_t mm = m[w];
-            while (mm) {
-              const int c = w * 32 + __ffs(mm) - 1;
-              g[c] = 0;
-              const uint32_t nc = (clr >> 24) & 3;
-              clr = (clr >> 31) ? clr
-                  : nc < 3 ? ((clr & 0x00ffffffu) | ((uint32_t)c << (8 * nc)) | ((nc + 1) << 24)) : (1u << 31);
-              mm &= mm - 1;
-            }
-          }
+          load_pool_row(reinterpret_cast<const uint4*>(v.pool + (size_t)s.scen * v.CS), pw, gw, v.CS);
+          clr.clear();
+          apply_mask_to_row(m, g, clr);                 // cells cleared this episode
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -363,12 +274,8 @@ __global__ __launch_bounds__(NT, WPE) void rollout_kernel(SimView v, RolloutArgs
         const unsigned long long t0 = CRAFT_NOW();
         const int64_t r = (a.tick0 + k) % a.ring;
         void* out = static_cast<uint8_t*>(a.obs) + r * n * (int64_t)F * esz;
-#ifndef CRAFT_ABL_NOE
         stream_obs<FMT, NT - 64, true>(s_obs + ((k - k0) & 1) * obs_buf, out, env0, F, nE,
                                        v.obs_policy, et);
-#else
-        (void)out;
-#endif
         const unsigned long long t1 = CRAFT_NOW();
         PACC(4, t1 - t0);
         __syncthreads();
@@ -394,34 +301,9 @@ __global__ __launch_bounds__(NT, WPE) void rollout_kernel(SimView v, RolloutArgs
     const bool handoff = c + 1 < n_chunks;
     if (tid < TILE && live) {
       // this episode's cleared cells: non-empty in pool[scenario], empty in the grid row
-      uint32_t m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int q = 0; q < (v.CS >> 2); ++q) {
-        const uint32_t p = pw[q], cc = gw[q];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          const bool cleared = ((p >> (8 * b)) & 0xffu) != 0 && ((cc >> (8 * b)) & 0xffu) == 0;
-          const int cell = 4 * q + b;
-          if (cleared) m[cell >> 5] |= 1u << (cell & 31);
-        }
-      }
-      if (handoff && state_only) {
-        typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-        const __amdgpu_buffer_rsrc_t inv_r = __builtin_amdgcn_make_buffer_rsrc(v.inv, 0, 0x7fffffff, 0x00020000);
-        const __amdgpu_buffer_rsrc_t msk_r = __builtin_amdgcn_make_buffer_rsrc(v.mask, 0, 0x7fffffff, 0x00020000);
-        const int off = (int)(slot * 32);
-        __hip_atomic_store((gu64*)(v.state + slot), (unsigned long long)st, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_raw_buffer_store_b128(u4v{ivw[0], ivw[1], ivw[2], ivw[3]}, inv_r, off, 0, 16);
-        __builtin_amdgcn_raw_buffer_store_b128(u4v{ivw[4], ivw[5], ivw[6], ivw[7]}, inv_r, off + 16, 0, 16);
-        __builtin_amdgcn_raw_buffer_store_b128(u4v{m[0], m[1], m[2], m[3]}, msk_r, off, 0, 16);
-        __builtin_amdgcn_raw_buffer_store_b128(u4v{m[4], m[5], m[6], m[7]}, msk_r, off + 16, 0, 16);
-      } else {
-        v.state[slot] = st;
-        v.inv[2 * slot] = make_uint4(ivw[0], ivw[1], ivw[2], ivw[3]);
-        v.inv[2 * slot + 1] = make_uint4(ivw[4], ivw[5], ivw[6], ivw[7]);
-        v.mask[2 * slot] = make_uint4(m[0], m[1], m[2], m[3]);
-        v.mask[2 * slot + 1] = make_uint4(m[4], m[5], m[6], m[7]);
-      }
+      uint32_t m[8];
+      cleared_mask(pw, gw, v.C, m);
+      publish_state(v, slot, st, ivw, m, handoff && state_only);
     }
     if (handoff && state_only) {
       if (tid < 64) {
@@ -447,12 +329,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_kernel(SimView v, RolloutArgs
 #undef PACC_C
 
   STAMP_END();
-  if (tid == 0) {
-    unsigned long long* srow = reinterpret_cast<unsigned long long*>(v.stats_part + 4 * (int64_t)blockIdx.x);
-    atomicAdd(srow + 0, (unsigned long long)n_succ);
-    atomicAdd(srow + 1, (unsigned long long)n_end);
-    atomicAdd(srow + 2, (unsigned long long)n_step);
-  }
+  if (tid == 0) add_stats(v, (int64_t)blockIdx.x, n_succ, n_end, n_step);
 }
 
 // Host side of one window.  Waves per SIMD: the producer wave of w=3 fits 128
@@ -509,30 +386,31 @@ static hipError_t launch_rollout_split_one(const SimView& v, const RolloutArgs& 
   return hipGetLastError();
 }
 
-template <int WIN, int TILE, int NT>
-static hipError_t launch_rollout_split(const SimView& v, const RolloutArgs& a, hipStream_t st) {
+// The handle's observation format and whether the actions are given, as template arguments:
+// f(std::integral_constant<int, FMT>, std::bool_constant<GIVEN>).
+template <class F>
+static hipError_t dispatch_fmt_given(const SimView& v, const RolloutArgs& a, F f) {
   const bool given = a.actions != nullptr;
+  auto with_fmt = [&](auto fmt) { return given ? f(fmt, std::true_type{}) : f(fmt, std::false_type{}); };
   switch (v.obs_fmt) {
-    case CRAFT_OBS_BF16: return given ? launch_rollout_split_one<WIN, TILE, NT, CRAFT_OBS_BF16, true>(v, a, st)
-                                      : launch_rollout_split_one<WIN, TILE, NT, CRAFT_OBS_BF16, false>(v, a, st);
-    case CRAFT_OBS_U8: return given ? launch_rollout_split_one<WIN, TILE, NT, CRAFT_OBS_U8, true>(v, a, st)
-                                    : launch_rollout_split_one<WIN, TILE, NT, CRAFT_OBS_U8, false>(v, a, st);
-    default: return given ? launch_rollout_split_one<WIN, TILE, NT, CRAFT_OBS_F32, true>(v, a, st)
-                          : launch_rollout_split_one<WIN, TILE, NT, CRAFT_OBS_F32, false>(v, a, st);
+    case CRAFT_OBS_BF16: return with_fmt(std::integral_constant<int, CRAFT_OBS_BF16>{});
+    case CRAFT_OBS_U8: return with_fmt(std::integral_constant<int, CRAFT_OBS_U8>{});
+    default: return with_fmt(std::integral_constant<int, CRAFT_OBS_F32>{});
   }
 }
 
 template <int WIN, int TILE, int NT>
+static hipError_t launch_rollout_split(const SimView& v, const RolloutArgs& a, hipStream_t st) {
+  return dispatch_fmt_given(v, a, [&](auto fmt, auto given) {
+    return launch_rollout_split_one<WIN, TILE, NT, decltype(fmt)::value, decltype(given)::value>(v, a, st);
+  });
+}
+
+template <int WIN, int TILE, int NT>
 static hipError_t launch_rollout_fmt(const SimView& v, const RolloutArgs& a, size_t lds, hipStream_t st) {
-  const bool given = a.actions != nullptr;
-  switch (v.obs_fmt) {
-    case CRAFT_OBS_BF16: return given ? launch_rollout_one<WIN, TILE, NT, CRAFT_OBS_BF16, true>(v, a, lds, st)
-                                      : launch_rollout_one<WIN, TILE, NT, CRAFT_OBS_BF16, false>(v, a, lds, st);
-    case CRAFT_OBS_U8: return given ? launch_rollout_one<WIN, TILE, NT, CRAFT_OBS_U8, true>(v, a, lds, st)
-                                    : launch_rollout_one<WIN, TILE, NT, CRAFT_OBS_U8, false>(v, a, lds, st);
-    default: return given ? launch_rollout_one<WIN, TILE, NT, CRAFT_OBS_F32, true>(v, a, lds, st)
-                          : launch_rollout_one<WIN, TILE, NT, CRAFT_OBS_F32, false>(v, a, lds, st);
-  }
+  return dispatch_fmt_given(v, a, [&](auto fmt, auto given) {
+    return launch_rollout_one<WIN, TILE, NT, decltype(fmt)::value, decltype(given)::value>(v, a, lds, st);
+  });
 }
 
 // threads per tile workgroup: 0 = the default of the tile width, else 128 / 256 / 512.

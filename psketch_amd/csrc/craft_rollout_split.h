@@ -33,6 +33,7 @@
 #pragma once
 #include <type_traits>
 
+#include "craft_episode.h"
 #include "craft_obs.h"
 
 namespace craft {
@@ -84,50 +85,26 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
   const int tid = threadIdx.x;
   const int64_t n = v.n_envs;
   const bool want_obs = a.obs != nullptr;
-  constexpr int esz = FMT == CRAFT_OBS_F32 ? 4 : (FMT == CRAFT_OBS_BF16 ? 2 : 1);
+  constexpr int esz = obs_elem_bytes(FMT);
   const int n_tiles = (int)((n + TILE - 1) / TILE);
   const int n_chunks = (a.n_ticks + a.chunk - 1) / a.chunk;
   const uint32_t n_units = (uint32_t)n_tiles * (uint32_t)n_chunks;
 
-  // wave 0, one lane per env (see craft_rollout.h for st / init_word / task_word / clr)
+  // wave 0, one lane per env (craft_rollout.h: st / init_word / task_word; craft_episode.h: ClearList)
   Agent s{};
   uint64_t st = 0;
   uint32_t init_word = 0, task_word = 0;
-  uint32_t clr = 0;          // cells cleared this episode (<= 3 ids, count, bit 31 = more)
-  uint32_t clr_prev = 0;     // the episode's clears before a restart (for the other buffer)
+  ClearList clr;             // cells cleared this episode
+  ClearList clr_prev;        // the episode's clears before a restart (for the other buffer)
   uint32_t chg = 0;          // what the last C did to its buffer: 0 nothing, 1 + cell cleared, kRestart
   constexpr uint32_t kRestart = 0x80000000u;
   int sync = 0;              // how C brings its buffer up to date: 0 loaded, 1 whole copy, 2 from chg
   bool live = false;
   int64_t slot = 0;
   const uint32_t* pw = reinterpret_cast<const uint32_t*>(s_pristine + tid * GS);
-  const uint8_t* pr = s_pristine + tid * GS;
   auto grid_of = [&](int p) __attribute__((always_inline)) { return s_grid + (p & 1) * TILE * GS + tid * GS; };
   auto inv_of = [&](int p) __attribute__((always_inline)) { return s_inv + (p & 1) * TILE * kInvStride + tid * kInvStride; };
   uint32_t n_succ = 0, n_end = 0, n_step = 0;
-
-  // restore the cells of `cl` (or the whole row) of grid row g from the pristine row
-  auto restore = [&](uint8_t* g, uint32_t cl) __attribute__((always_inline)) {
-    if (cl >> 31) {
-      uint32_t* gw = reinterpret_cast<uint32_t*>(g);
-      for (int q0 = 0; q0 < (v.CS >> 2); q0 += 12) {
-        uint32_t w[12];
-#pragma unroll
-        for (int j = 0; j < 12; ++j) w[j] = q0 + j < (v.CS >> 2) ? pw[q0 + j] : 0u;
-#pragma unroll
-        for (int j = 0; j < 12; ++j)
-          if (q0 + j < (v.CS >> 2)) gw[q0 + j] = w[j];
-      }
-    } else {
-      const int nc = (cl >> 24) & 3;
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if (i < nc) {
-          const int c = (cl >> (8 * i)) & 0xff;
-          g[c] = pr[c];
-        }
-    }
-  };
 
   // ---- C: tick k on buffer p & 1 (trainers/imitation.py:59-73); p = the item index --------------
   auto tick_c = [&](int k, int p, bool lds_out) __attribute__((always_inline)) {
@@ -140,18 +117,9 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
     if (live) {
       // bring this buffer up to the other buffer's state: whole row after a load, else its last change
       if (sync == 1) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(grid_of(p ^ 1));
-        uint32_t* gw = reinterpret_cast<uint32_t*>(g);
-        for (int q0 = 0; q0 < (v.CS >> 2); q0 += 12) {
-          uint32_t w[12];
-#pragma unroll
-          for (int j = 0; j < 12; ++j) w[j] = q0 + j < (v.CS >> 2) ? src[q0 + j] : 0u;
-#pragma unroll
-          for (int j = 0; j < 12; ++j)
-            if (q0 + j < (v.CS >> 2)) gw[q0 + j] = w[j];
-        }
+        copy_row_words(reinterpret_cast<uint32_t*>(g), reinterpret_cast<const uint32_t*>(grid_of(p ^ 1)), v.CS);
       } else if (sync == 2) {
-        if (chg == kRestart) restore(g, clr_prev);
+        if (chg == kRestart) clr_prev.restore(g, pw, v.CS);
         else if (chg) g[chg - 1] = 0;
       }
       if (sync) {
@@ -164,78 +132,40 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
       }
       sync = sync ? 2 : 1;
       chg = 0;
-      int act;
-      if (GIVEN) {
-        act = a.actions[(int64_t)k * n + slot];
-      } else {
-        const uint64_t gid = (uint64_t)(v.env_base + slot);
-        act = (int)((uint32_t)(splitmix64(a.seed ^ (gid << 20) ^ (uint64_t)tick) >> 32) % 6u);
-      }
+      const int act = GIVEN ? a.actions[(int64_t)k * n + slot] : hashed_action(v, a.seed, slot, tick);
       bool restart = false;
-      if (s.frozen) {
-        d = 1;
-      } else {
-        counted = 1;
-        s.timer -= 1;
-        d = (act == CRAFT_STOP) || s.timer <= 0;
-        restart = d && (a.flags & CRAFT_STEP_AUTORESET);
-      }
-      if (d) {                                          // satisfies() of the pre-step state
-        const int goal = task_word & 0xf, arg = (task_word >> 4) & 0xff;
-        const int fc = (s.x + dir_dx(s.dir)) * v.H + (s.y + dir_dy(s.dir));
-        if (goal == CRAFT_GOAL_GET || goal == CRAFT_GOAL_MAKE) succ = iv[arg] > 0;
-        else if (goal == CRAFT_GOAL_GO) succ = (int)g[fc] == arg;
-        else succ = -1;
-      }
-      if (restart) {                                    // CraftScenario.init, craft.py:268-273
-        s.x = init_word & 0xff; s.y = (init_word >> 8) & 0xff; s.dir = (init_word >> 16) & 3;
-        s.timer = v.maxT;
+      protocol_step(s, act, a.flags, d, counted, restart);
+      if (d) succ = satisfies(v, g, iv, s, task_word);  // of the pre-step state
+      if (restart) {
+        restart_agent(s, init_word, v.maxT);
 #pragma unroll
         for (int w = 0; w < 8; ++w) reinterpret_cast<uint32_t*>(iv)[w] = 0u;
-        restore(g, clr);
+        clr.restore(g, pw, v.CS);
         clr_prev = clr;
-        clr = 0;
+        clr.clear();
         chg = kRestart;
       } else if (d && !s.frozen) {
-        s.frozen = 1;
-        s.timer = max(s.timer, 0);
+        freeze_agent(s);
       }
       if (!d) {
         bool inv_changed = false, mask_changed = false;
         uint32_t m_unused[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int fc = (s.x + dir_dx(s.dir)) * v.H + (s.y + dir_dy(s.dir));   // what USE clears
-#ifndef CRAFT_ABL_NOTRANS
+        const int fc = facing_cell(s, v.H);             // what USE clears
         if (act < 0 || act >= CRAFT_N_ACTIONS) latch_error(v.err, CRAFT_EBADACTION, slot);
         else transition<true>(v, s_rc, g, iv, s, m_unused, act, inv_changed, mask_changed, rcv, slot);
-#endif
         if (mask_changed) {
           chg = 1u + (uint32_t)fc;
-          const uint32_t nc = (clr >> 24) & 3;
-          clr = (clr >> 31) ? clr
-              : nc < 3 ? ((clr & 0x00ffffffu) | ((uint32_t)fc << (8 * nc)) | ((nc + 1) << 24)) : (1u << 31);
+          clr.push(fc);
         }
       }
       st = pack_state(s);
-      if (lds_out) {                                    // stored by the streaming waves with E
-        s_out[(p & 3) * TILE + tid] = (uint32_t)(uint8_t)d | ((uint32_t)(uint8_t)(int8_t)succ << 8) |
-                                      ((uint32_t)(counted && d && succ == 1) << 16) | (1u << 24);
-      } else {
-        const int64_t o = r * n + slot;
-        if (a.done) a.done[o] = (uint8_t)d;
-        if (a.sat) a.sat[o] = (int8_t)succ;
-        if (a.reward) a.reward[o] = (counted && d && succ == 1) ? 1.0f : 0.0f;
-      }
+      if (lds_out) s_out[(p & 3) * TILE + tid] = pack_outputs(d, succ, counted);   // stored by the streaming waves with E
+      else store_outputs(a, r * n + slot, d, succ, counted);
     } else if (lds_out && tid < TILE) {
       s_out[(p & 3) * TILE + tid] = 0u;
     }
-    const uint64_t bs = __ballot(live && counted && d && succ == 1);
-    const uint64_t be = __ballot(live && counted && d);
-    const uint64_t bt = __ballot(live && counted);
-    n_succ += (uint32_t)__popcll(bs);
-    n_end += (uint32_t)__popcll(be);
-    n_step += (uint32_t)__popcll(bt);
-    s_agent[(p & 1) * TILE + tid] =
-        live ? ((uint32_t)s.x | ((uint32_t)s.y << 8) | ((uint32_t)s.dir << 16) | (1u << 24)) : 0u;
+    tally_stats(live, counted, d, succ, n_succ, n_end, n_step);
+    s_agent[(p & 1) * TILE + tid] = agent_word(s, live);
   };
 
   // ---- A: lanes < TILE of wave 0 take over tile t into buffer p (state, pool row, clears) -----
@@ -277,14 +207,14 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
       m[0] = m0.x; m[1] = m0.y; m[2] = m0.z; m[3] = m0.w;
       m[4] = m1.x; m[5] = m1.y; m[6] = m1.z; m[7] = m1.w;
       s = unpack_state(st);
-      if (s.x < 1 || s.x > v.W - 2 || s.y < 1 || s.y > v.H - 2 || s.scen >= v.pool_count) {
+      if (!state_in_range(v, s)) {
         latch_error(v.err, CRAFT_EINVAL, slot);
         live = false;
       }
     }
     chg = 0;
-    clr = 0;
-    clr_prev = 0;
+    clr.clear();
+    clr_prev.clear();
     sync = 0;
     if (live) {
       task_word = s_task[s.task];
@@ -303,39 +233,13 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
           pwm[q + 2] = g0[q + 2] = c.z;
           pwm[q + 3] = g0[q + 3] = c.w;
         }
-      } else {                                          // HBM / L2: four chunks in flight
-        for (int q0 = 0; q0 < nchunk; q0 += 4) {
-          uint4 cq[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (q0 + j < nchunk) cq[j] = gsrc[q0 + j];
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (q0 + j < nchunk) {
-              const int q = 4 * (q0 + j);
-              pwm[q + 0] = g0[q + 0] = cq[j].x;
-              pwm[q + 1] = g0[q + 1] = cq[j].y;
-              pwm[q + 2] = g0[q + 2] = cq[j].z;
-              pwm[q + 3] = g0[q + 3] = cq[j].w;
-            }
-        }
+      } else {                                          // HBM / L2
+        load_pool_row(gsrc, pwm, g0, v.CS);
       }
       uint32_t* iv0 = reinterpret_cast<uint32_t*>(inv_of(p));
 #pragma unroll
       for (int i = 0; i < 8; ++i) iv0[i] = ivr[i];
-      uint8_t* b0 = grid_of(p);
-#pragma unroll
-      for (int w = 0; w < 8; ++w) {                     // cells cleared this episode
-        uint32_t mm = m[w];
-        while (mm) {
-          const int cc = w * 32 + __ffs(mm) - 1;
-          b0[cc] = 0;
-          const uint32_t nc = (clr >> 24) & 3;
-          clr = (clr >> 31) ? clr
-              : nc < 3 ? ((clr & 0x00ffffffu) | ((uint32_t)cc << (8 * nc)) | ((nc + 1) << 24)) : (1u << 31);
-          mm &= mm - 1;
-        }
-      }
+      apply_mask_to_row(m, grid_of(p), clr);            // cells cleared this episode
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -343,53 +247,18 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
   };
 
   // ---- the tile's state back to HBM from buffer p (its last item); the mask is rebuilt from
-  // the rows: cells are only ever cleared, so mask = {c : pristine[c] != 0 and grid[c] == 0} ---
-  // cleared = pristine byte nonzero and current byte zero, 4 cells per word (SWAR); fully
-  // unrolled so every mask word index is static
-  auto cleared_mask = [&](int p, uint32_t (&m)[8]) __attribute__((always_inline)) {
-    const uint32_t* gw = reinterpret_cast<const uint32_t*>(grid_of(p));
-#pragma unroll
-    for (int i = 0; i < 8; ++i) m[i] = 0u;
-#pragma unroll
-    for (int q = 0; q < CRAFT_MAX_CELLS / 4; ++q)
-      if (q < (v.C + 3) >> 2)
-        m[q >> 3] |= byte_tops(nonzero_bytes(pw[q]) & zero_bytes(gw[q])) << (4 * (q & 7));
-  };
+  // the rows (cleared_mask, craft_episode.h) ---
   auto publish = [&](int p, bool sc1) __attribute__((always_inline)) {
-    const uint32_t* ivw = reinterpret_cast<const uint32_t*>(inv_of(p));
     uint32_t m[8];
-    cleared_mask(p, m);
-    if (sc1) {
-      // write-through (sc1) stores: the hand-off form of MI355X_MICROARCH.md "Valid forms"
-      // ({sc1 stores} -> every storing wave's s_waitcnt vmcnt(0) -> one lane's flag)
-      typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-      const __amdgpu_buffer_rsrc_t inv_r = __builtin_amdgcn_make_buffer_rsrc(v.inv, 0, 0x7fffffff, 0x00020000);
-      const __amdgpu_buffer_rsrc_t msk_r = __builtin_amdgcn_make_buffer_rsrc(v.mask, 0, 0x7fffffff, 0x00020000);
-      const int off = (int)(slot * 32);
-      __hip_atomic_store((gu64*)(v.state + slot), (unsigned long long)st, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_raw_buffer_store_b128(u4v{ivw[0], ivw[1], ivw[2], ivw[3]}, inv_r, off, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b128(u4v{ivw[4], ivw[5], ivw[6], ivw[7]}, inv_r, off + 16, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b128(u4v{m[0], m[1], m[2], m[3]}, msk_r, off, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b128(u4v{m[4], m[5], m[6], m[7]}, msk_r, off + 16, 0, 16);
-    } else {
-      v.state[slot] = st;
-      v.inv[2 * slot] = make_uint4(ivw[0], ivw[1], ivw[2], ivw[3]);
-      v.inv[2 * slot + 1] = make_uint4(ivw[4], ivw[5], ivw[6], ivw[7]);
-      v.mask[2 * slot] = make_uint4(m[0], m[1], m[2], m[3]);
-      v.mask[2 * slot + 1] = make_uint4(m[4], m[5], m[6], m[7]);
-    }
+    cleared_mask(pw, reinterpret_cast<const uint32_t*>(grid_of(p)), v.C, m);
+    publish_state(v, slot, st, reinterpret_cast<const uint32_t*>(inv_of(p)), m, sc1);
   };
 
   // ---- D on wave 1: lane l scatters part l / TILE of env l % TILE of the item in buffer p ----
   auto scatter_d = [&](int p, int nE) __attribute__((always_inline)) {
     const int l = tid - 64, e = l % TILE;
     const uint32_t ag = s_agent[(p & 1) * TILE + e];
-#ifdef CRAFT_ABL_NOD
-    if (false)
-#else
     if (e < nE && ag)
-#endif
       scatter_env_part<WIN, P>(v, s_grid + (p & 1) * TILE * GS + e * GS,
                                s_inv + (p & 1) * TILE * kInvStride + e * kInvStride, ag,
                                s_obs + (p & 1) * obs_buf + e * F, l / TILE);
@@ -402,6 +271,8 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
     const int64_t r = (a.tick0 + k) % a.ring;
     if (outs && tid - 128 < nE) {                       // the tick's done / success / reward (flat pipeline)
       const uint32_t w = s_out[(p & 3) * TILE + tid - 128];
+      // (pack_outputs' word taken apart in place, not through a helper: as one, the continuous
+      // pipeline's instantiation took one more VGPR)
       if (w >> 24) {
         const int64_t o = r * n + env0 + (tid - 128);
         if (a.done) a.done[o] = (uint8_t)(w & 0xffu);
@@ -410,12 +281,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
       }
     }
     void* out = static_cast<uint8_t*>(a.obs) + r * n * (int64_t)F * esz;
-#ifndef CRAFT_ABL_NOE
     stream_obs<FMT, NT - 128, true>(s_obs + (p & 1) * obs_buf, out, env0, F, nE, v.obs_policy, tid - 128);
-#else
-    (void)out;
-    (void)nE;
-#endif
   };
 
   // ---- once per workgroup: task table, cleared observation rows --------------------------------
@@ -510,7 +376,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
         const int64_t pslot = slot;
         if (pub) {
           uint32_t m[8];
-          cleared_mask((j - 1) & 1, m);
+          cleared_mask(pw, reinterpret_cast<const uint32_t*>(grid_of(j - 1)), v.C, m);
           ob_state[tid] = st;
 #pragma unroll
           for (int i = 0; i < 8; ++i) ob_mask[8 * tid + i] = m[i];
@@ -556,13 +422,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
       }
       if (have && tid < TILE) tick_c(cur_k, j, true);
       if (pub_slot >= 0) {                              // the finished tile's state, last: nothing waits on it
-        const uint32_t* ivw = reinterpret_cast<const uint32_t*>(inv_of((j - 1) & 1));
-        const uint32_t* mw = ob_mask + 8 * tid;
-        v.state[pub_slot] = ob_state[tid];
-        v.inv[2 * pub_slot] = make_uint4(ivw[0], ivw[1], ivw[2], ivw[3]);
-        v.inv[2 * pub_slot + 1] = make_uint4(ivw[4], ivw[5], ivw[6], ivw[7]);
-        v.mask[2 * pub_slot] = make_uint4(mw[0], mw[1], mw[2], mw[3]);
-        v.mask[2 * pub_slot + 1] = make_uint4(mw[4], mw[5], mw[6], mw[7]);
+        publish_state(v, pub_slot, ob_state[tid], reinterpret_cast<const uint32_t*>(inv_of(j - 1)), ob_mask + 8 * tid, false);
         pub_slot = -1;
       }
       if (tid == 0) {
@@ -764,12 +624,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
 #endif
   }
 
-  if (tid == 0) {
-    unsigned long long* srow = reinterpret_cast<unsigned long long*>(v.stats_part + 4 * (int64_t)blockIdx.x);
-    atomicAdd(srow + 0, (unsigned long long)n_succ);
-    atomicAdd(srow + 1, (unsigned long long)n_end);
-    atomicAdd(srow + 2, (unsigned long long)n_step);
-  }
+  if (tid == 0) add_stats(v, (int64_t)blockIdx.x, n_succ, n_end, n_step);
 }
 
 }  // namespace craft

@@ -46,6 +46,7 @@
 // Results are identical to n_ticks craft_step_teach calls with the same action sources (tests:
 // tests/test_gpu_rollout_teach.py, tick by tick at 65,536 envs and against the oracle).
 #pragma once
+#include "craft_episode.h"
 #include "craft_host.h"
 #include "craft_obs.h"
 #include "craft_teach.h"
@@ -280,7 +281,8 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
     Agent s{};
     uint64_t st = 0;
     uint32_t init_word = 0, task_word = 0, conn = 0;
-    uint32_t clr = 0, clr_prev = 0, chg = 0;
+    ClearList clr, clr_prev;          // this episode's clears; those before a restart (craft_episode.h)
+    uint32_t chg = 0;
     uint32_t clk = 0, clk_prev = 0;   // the kinds of clr's (up to 3) cells before they were cleared
     constexpr uint32_t kRestart = 0x80000000u;
     int sync = 0, lab0 = 0;
@@ -310,26 +312,9 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
       nbw = (uint32_t)g[p - 1] | ((uint32_t)g[p + 1] << 8) | ((uint32_t)g[p - H] << 16) | ((uint32_t)g[p + H] << 24);
     };
     auto inv_of = [&](int p) __attribute__((always_inline)) { return s_inv + (p & 1) * TILE * kInvStride + lane * kInvStride; };
-    auto restore = [&](uint8_t* g, uint32_t cl, uint32_t ck) __attribute__((always_inline)) {
-      if (cl >> 31) {
-        uint32_t* gw = reinterpret_cast<uint32_t*>(g);
-        for (int q0 = 0; q0 < (v.CS >> 2); q0 += 12) {
-          uint32_t w[12];
-#pragma unroll
-          for (int j = 0; j < 12; ++j) w[j] = q0 + j < (v.CS >> 2) ? pw[q0 + j] : 0u;
-#pragma unroll
-          for (int j = 0; j < 12; ++j)
-            if (q0 + j < (v.CS >> 2)) gw[q0 + j] = w[j];
-        }
-      } else {
-        const int nc = (cl >> 24) & 3;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-          if (i < nc) {
-            const int c = (cl >> (8 * i)) & 0xff;
-            g[c] = (uint8_t)(ck >> (8 * i));                         // (no read of the pristine row)
-          }
-      }
+    // (the listed cells from their recorded kinds: no read of the pristine row)
+    auto restore = [&](uint8_t* g, const ClearList& cl, uint32_t ck) __attribute__((always_inline)) {
+      cl.restore(g, pw, v.CS, [&](int i, int) __attribute__((always_inline)) { return (uint8_t)(ck >> (8 * i)); });
     };
     // ---- A: take over tile t into buffer 0 ----
     auto load_tile = [&](int t) __attribute__((always_inline)) {
@@ -354,14 +339,14 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
         m[4] = m1.x; m[5] = m1.y; m[6] = m1.z; m[7] = m1.w;
         lsrc = a.label_actions || (bcw & 0xffu);
         s = unpack_state(st);
-        if (s.x < 1 || s.x > v.W - 2 || s.y < 1 || s.y > v.H - 2 || s.scen >= v.pool_count) {
+        if (!state_in_range(v, s)) {
           latch_error(v.err, CRAFT_EINVAL, slot);
           live = false;
         }
       }
       chg = 0;
-      clr = 0;
-      clr_prev = 0;
+      clr.clear();
+      clr_prev.clear();
       clk = 0;
       clk_prev = 0;
       sync = 0;
@@ -380,42 +365,17 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
         ncl = 0;
 #pragma unroll
         for (int w = 0; w < 8; ++w) ncl += __popc(m[w]);
-        uint32_t* g0 = reinterpret_cast<uint32_t*>(grid_of(0));
-        uint32_t* pwm = reinterpret_cast<uint32_t*>(s_pristine + lane * GS);
-        const uint4* gsrc = reinterpret_cast<const uint4*>(v.pool + (size_t)s.scen * v.CS);
-        const int nchunk = v.CS >> 4;
-        for (int q0 = 0; q0 < nchunk; q0 += 4) {
-          uint4 cq[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (q0 + j < nchunk) cq[j] = gsrc[q0 + j];
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (q0 + j < nchunk) {
-              const int q = 4 * (q0 + j);
-              pwm[q + 0] = g0[q + 0] = cq[j].x;
-              pwm[q + 1] = g0[q + 1] = cq[j].y;
-              pwm[q + 2] = g0[q + 2] = cq[j].z;
-              pwm[q + 3] = g0[q + 3] = cq[j].w;
-            }
-        }
+        load_pool_row(reinterpret_cast<const uint4*>(v.pool + (size_t)s.scen * v.CS),
+                      reinterpret_cast<uint32_t*>(s_pristine + lane * GS), reinterpret_cast<uint32_t*>(grid_of(0)), v.CS);
         uint32_t* iv0 = reinterpret_cast<uint32_t*>(inv_of(0));
 #pragma unroll
         for (int i = 0; i < 8; ++i) iv0[i] = ivn[i] = ivr[i];
         uint8_t* b0 = grid_of(0);
-#pragma unroll
-        for (int w = 0; w < 8; ++w) {                                  // cells cleared this episode
-          uint32_t mm = m[w];
-          while (mm) {
-            const int cc = w * 32 + __ffs(mm) - 1;
-            b0[cc] = 0;
-            const uint32_t nc = (clr >> 24) & 3;
-            if (!(clr >> 31) && nc < 3) clk |= (uint32_t)pr[cc] << (8 * nc);
-            clr = (clr >> 31) ? clr
-                : nc < 3 ? ((clr & 0x00ffffffu) | ((uint32_t)cc << (8 * nc)) | ((nc + 1) << 24)) : (1u << 31);
-            mm &= mm - 1;
-          }
-        }
+        for_each_masked_cell(m, [&](int cc) __attribute__((always_inline)) {   // cells cleared this episode
+          b0[cc] = 0;
+          if (clr.has_room()) clk |= (uint32_t)pr[cc] << (8 * clr.count());
+          clr.push(cc);
+        });
         read_nb(b0);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -434,10 +394,10 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
       for (int w = 0; w < 8; ++w) have |= byte_tops(nonzero_bytes(ivw[w])) << (4 * w);
       // the listed cells cleared: from the episode's cleared-cell list (clr), or the grid past 3
       uint32_t cleared = 0;
-      if (!(clr >> 31)) {
-        const uint32_t nc = (clr >> 24) & 3;
-        const uint32_t k0 = nc > 0 ? (clr & 0xffu) : 0x100u, k1 = nc > 1 ? ((clr >> 8) & 0xffu) : 0x100u,
-                       k2 = nc > 2 ? ((clr >> 16) & 0xffu) : 0x100u;
+      if (!clr.overflowed()) {
+        const uint32_t nc = clr.count();
+        const uint32_t k0 = nc > 0 ? (uint32_t)clr.cell(0) : 0x100u, k1 = nc > 1 ? (uint32_t)clr.cell(1) : 0x100u,
+                       k2 = nc > 2 ? (uint32_t)clr.cell(2) : 0x100u;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const uint32_t c = ((j < 4 ? c_cw.x : c_cw.y) >> (8 * (j & 3))) & 0xffu;
@@ -531,16 +491,7 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
       const uint64_t tc0 = RT_CLK();
       if (live) {
         if (sync == 1) {                                               // bring the buffer up to date
-          const uint32_t* src = reinterpret_cast<const uint32_t*>(grid_of(k + 1));
-          uint32_t* gw = reinterpret_cast<uint32_t*>(gr);
-          for (int q0 = 0; q0 < (v.CS >> 2); q0 += 12) {
-            uint32_t w[12];
-#pragma unroll
-            for (int j = 0; j < 12; ++j) w[j] = q0 + j < (v.CS >> 2) ? src[q0 + j] : 0u;
-#pragma unroll
-            for (int j = 0; j < 12; ++j)
-              if (q0 + j < (v.CS >> 2)) gw[q0 + j] = w[j];
-          }
+          copy_row_words(reinterpret_cast<uint32_t*>(gr), reinterpret_cast<const uint32_t*>(grid_of(k + 1)), v.CS);
         } else if (sync == 2) {
           if (chg == kRestart) restore(gr, clr_prev, clk_prev);
           else if (chg) gr[chg - 1] = 0;
@@ -553,50 +504,33 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
         chg = 0;
         RT_ACC(4, tc0);
         const uint64_t tc1 = RT_CLK();
-        if (a.actions) {
-          act = a.actions[(int64_t)k * n + slot];
-        } else {
-          const uint64_t gid = (uint64_t)(v.env_base + slot);
-          act = (int)((uint32_t)(splitmix64(a.seed ^ (gid << 20) ^ (uint64_t)tick) >> 32) % 6u);
-        }
+        act = a.actions ? a.actions[(int64_t)k * n + slot] : hashed_action(v, a.seed, slot, tick);
         if (lsrc) act = k == 0 ? lab0 : use_row ? (int)s_rows[((g - 1) & (kRtRows - 1)) * RW + 4 + lane] : clab;
         bool restart = false;
-        if (s.frozen) {
-          d = 1;
-        } else {
-          counted = 1;
-          s.timer -= 1;
-          d = (act == CRAFT_STOP) || s.timer <= 0;
-          restart = d && (a.flags & CRAFT_STEP_AUTORESET);
-        }
-        if (d) {                                                       // satisfies() of the pre-step state
-          const int goal = task_word & 0xf, arg = (task_word >> 4) & 0xff;
-          const int fc = (s.x + dir_dx(s.dir)) * H + (s.y + dir_dy(s.dir));
-          if (goal == CRAFT_GOAL_GET || goal == CRAFT_GOAL_MAKE) succ = rbyte(ivn, arg) > 0;
-          else if (goal == CRAFT_GOAL_GO) succ = (int)gr[fc] == arg;
-          else succ = -1;
-        }
-        if (restart) {                                                 // CraftScenario.init, craft.py:268-273
-          s.x = init_word & 0xff; s.y = (init_word >> 8) & 0xff; s.dir = (init_word >> 16) & 3;
-          s.timer = v.maxT;
+        protocol_step(s, act, a.flags, d, counted, restart);
+        if (d)                                                         // satisfies() of the pre-step state
+          succ = satisfies_with(
+              task_word, [&](int arg) __attribute__((always_inline)) { return rbyte(ivn, arg); },
+              [&]() __attribute__((always_inline)) { return (int)gr[facing_cell(s, H)]; });
+        if (restart) {
+          restart_agent(s, init_word, v.maxT);
 #pragma unroll
           for (int w = 0; w < 8; ++w) reinterpret_cast<uint32_t*>(iv)[w] = 0u;
           restore(gr, clr, clk);
           clr_prev = clr;
           clk_prev = clk;
-          clr = 0;
+          clr.clear();
           clk = 0;
           chg = kRestart;
           ncl = 0;
         } else if (d && !s.frozen) {
-          s.frozen = 1;
-          s.timer = max(s.timer, 0);
+          freeze_agent(s);
         }
         RT_ACC(5, tc1);
         const uint64_t tc2 = RT_CLK();
         if (!d) {
           bool inv_changed = false, mask_changed = false;
-          const int fc = (s.x + dir_dx(s.dir)) * H + (s.y + dir_dy(s.dir));   // what USE clears
+          const int fc = facing_cell(s, H);                              // what USE clears
           uint32_t m_unused[8] = {0, 0, 0, 0, 0, 0, 0, 0};
           if (act < 0 || act >= CRAFT_N_ACTIONS) latch_error(v.err, CRAFT_EBADACTION, slot);
           else if (v.wsr) transition<true, true, true>(v, s_rc, gr, iv, s, m_unused, act, inv_changed, mask_changed, rcv, slot, s_wsr, nbw);
@@ -604,10 +538,8 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
           if (mask_changed) {
             ++ncl;
             chg = 1u + (uint32_t)fc;
-            const uint32_t nc = (clr >> 24) & 3;
-            if (!(clr >> 31) && nc < 3) clk |= ((nbw >> (8 * s.dir)) & 0xffu) << (8 * nc);   // USE cleared the facing cell
-            clr = (clr >> 31) ? clr
-                : nc < 3 ? ((clr & 0x00ffffffu) | ((uint32_t)fc << (8 * nc)) | ((nc + 1) << 24)) : (1u << 31);
+            if (clr.has_room()) clk |= ((nbw >> (8 * s.dir)) & 0xffu) << (8 * clr.count());   // USE cleared the facing cell
+            clr.push(fc);
           }
         }
         st = pack_state(s);
@@ -624,36 +556,19 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
                                                    (uint32_t)(counted ? act : -1));
         RT_ACC(1, tc3);
       }
-      const uint64_t bs = __ballot(live && counted && d && succ == 1);
-      const uint64_t be = __ballot(live && counted && d);
-      const uint64_t bt = __ballot(live && counted);
-      n_succ += (uint32_t)__popcll(bs);
-      n_end += (uint32_t)__popcll(be);
-      n_step += (uint32_t)__popcll(bt);
+      tally_stats(live, counted, d, succ, n_succ, n_end, n_step);
       if (lane < TILE) {
         if (!live) s_cout[(k & 1) * TILE + lane] = make_uint2(0u, 0u);
         s_agent[(k & 1) * TILE + lane] =
-            live ? ((uint32_t)s.x | ((uint32_t)s.y << 8) | ((uint32_t)s.dir << 16) | (1u << 24) |
-                    ((uint32_t)s.frozen << 25) | ((uint32_t)min(ncl, 63) << 26))
-                 : 0u;
+            live ? (agent_word(s, true) | ((uint32_t)s.frozen << 25) | ((uint32_t)min(ncl, 63) << 26)) : 0u;
         s_tinfo[(k & 1) * TILE + lane] = (uint32_t)s.task | (conn << 8) | ((uint32_t)s.scen << 10);
       }
     };
     // ---- the tile's state back to HBM from buffer p (the mask rebuilt from the rows) ----
     auto publish = [&](int p) __attribute__((always_inline)) {
-      const uint32_t* ivw = reinterpret_cast<const uint32_t*>(inv_of(p));
-      const uint32_t* gw = reinterpret_cast<const uint32_t*>(grid_of(p));
       uint32_t m[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) m[i] = 0u;
-#pragma unroll
-      for (int q = 0; q < CRAFT_MAX_CELLS / 4; ++q)
-        if (q < (C + 3) >> 2) m[q >> 3] |= byte_tops(nonzero_bytes(pw[q]) & zero_bytes(gw[q])) << (4 * (q & 7));
-      v.state[slot] = st;
-      v.inv[2 * slot] = make_uint4(ivw[0], ivw[1], ivw[2], ivw[3]);
-      v.inv[2 * slot + 1] = make_uint4(ivw[4], ivw[5], ivw[6], ivw[7]);
-      v.mask[2 * slot] = make_uint4(m[0], m[1], m[2], m[3]);
-      v.mask[2 * slot + 1] = make_uint4(m[4], m[5], m[6], m[7]);
+      cleared_mask(pw, reinterpret_cast<const uint32_t*>(grid_of(p)), C, m);
+      publish_state(v, slot, st, reinterpret_cast<const uint32_t*>(inv_of(p)), m, false);
     };
     bool first = (uint32_t)blockIdx.x < n_units;
     uint32_t gbase = 0;
@@ -781,7 +696,7 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
         const uint64_t te = RT_CLK();
         if (i >= 1 && want_obs) {
           const int64_t r = (a.tick0 + i - 1) % a.ring;
-          void* out = static_cast<uint8_t*>(a.obs) + r * n * (int64_t)F * (v.obs_fmt == CRAFT_OBS_F32 ? 4 : v.obs_fmt == CRAFT_OBS_BF16 ? 2 : 1);
+          void* out = static_cast<uint8_t*>(a.obs) + r * n * (int64_t)F * obs_elem_bytes(v.obs_fmt);
           uint8_t* rows = s_obs + ((i - 1) & 1) * obs_buf;
           switch (v.obs_fmt) {
             case CRAFT_OBS_BF16: stream_obs<CRAFT_OBS_BF16, NE, true>(rows, out, env0, F, nE, v.obs_policy, et); break;
@@ -797,7 +712,7 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
           if (c.x & (1u << 4)) {
             if (wave == 3 && a.done) a.done[o] = (uint8_t)d;
             if (wave == 4 && a.sat) a.sat[o] = (int8_t)succ;
-            if (wave == 5 && a.reward) a.reward[o] = (counted && d && succ == 1) ? 1.0f : 0.0f;
+            if (wave == 5 && a.reward) a.reward[o] = rewarded(counted, d, succ) ? 1.0f : 0.0f;
             if (wave == 6 && a.rec) a.rec[o] = (int32_t)c.y;
           }
         }
@@ -1306,12 +1221,7 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
 #endif
 #undef RT_CLK
 #undef RT_ACC
-  if (tid == 0) {
-    unsigned long long* srow = reinterpret_cast<unsigned long long*>(v.stats_part + 4 * (int64_t)blockIdx.x);
-    atomicAdd(srow + 0, (unsigned long long)n_succ);
-    atomicAdd(srow + 1, (unsigned long long)n_end);
-    atomicAdd(srow + 2, (unsigned long long)n_step);
-  }
+  if (tid == 0) add_stats(v, (int64_t)blockIdx.x, n_succ, n_end, n_step);
 }
 
 }  // namespace craft

@@ -921,7 +921,7 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
   if (!s) return CRAFT_EINVAL;
   if (n_ticks < 0 || ring < 1 || tick0 < 0)
     return fail(s, CRAFT_EINVAL, "craft_rollout: need n_ticks >= 0, ring >= 1, tick0 >= 0");
-  const int esz = s->view.obs_fmt == CRAFT_OBS_F32 ? 4 : (s->view.obs_fmt == CRAFT_OBS_BF16 ? 2 : 1);
+  const int esz = craft::obs_elem_bytes(s->view.obs_fmt);
   if (obs && (!aligned16(obs) || (ring > 1 && (s->n_envs * (int64_t)s->view.F * esz) % 16 != 0)))
     return fail(s, CRAFT_EINVAL, "craft_rollout: every obs ring slot must be 16-byte aligned");
   craft::RolloutArgs a{};
@@ -995,7 +995,7 @@ int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, voi
   const bool lsync = x->label_actions != 0 || x->behavior_clone != nullptr;
   if (lsync && !x->label_in)
     return fail(s, CRAFT_EINVAL, "craft_rollout_teach: label_actions / behavior_clone need label_in");
-  const int esz = s->view.obs_fmt == CRAFT_OBS_F32 ? 4 : (s->view.obs_fmt == CRAFT_OBS_BF16 ? 2 : 1);
+  const int esz = craft::obs_elem_bytes(s->view.obs_fmt);
   if (x->obs && (!aligned16(x->obs) || (x->ring > 1 && (s->n_envs * (int64_t)s->view.F * esz) % 16 != 0)))
     return fail(s, CRAFT_EINVAL, "craft_rollout_teach: every obs ring slot must be 16-byte aligned");
   if (x->n_ticks == 0) return CRAFT_OK;

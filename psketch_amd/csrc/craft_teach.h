@@ -669,11 +669,6 @@ __device__ __forceinline__ int teach_env(const SimView& v, const uint16_t* task_
     }
     Bits<NW> occ, tgt;
     band_bits<NW, LANES>(row32, nq, C, H, m, (uint32_t)kind, ql, occ, tgt);
-#ifdef CRAFT_ABL_NOBFS
-    fa = (int)(occ.w[0] ^ tgt.w[NW - 1]) & 3;             // ablation build only: no BFS
-    len = 1;
-    return true;
-#endif
     return bfs_closest<NW, LANES>(occ, tgt, valid, H, s.x * H + s.y - H, s.dir, ql, fa, len, want_action, conn);
   };
   int leaf_kind = -1, leaf_fa = -1, leaf_len = -1;

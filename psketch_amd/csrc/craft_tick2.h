@@ -27,6 +27,7 @@
 // Results are identical to tile_kernel<WIN, MODE_TICK> + the teacher: the same tests run
 // both (craft_sim_tune_teach selects either kernel).
 #pragma once
+#include "craft_episode.h"
 #include "craft_obs.h"
 #include "craft_teach.h"
 
@@ -165,14 +166,11 @@ __global__ __launch_bounds__(64 * TW + J * kTick2Tile * TL, CRAFT_T2_WPE) void t
         if (lane + 64 * q < v.n_tasks * CRAFT_MAX_SUBTASKS) s_tsub[lane + 64 * q] = sw[q];
     }
     if (live) {
-      if (!a.actions) {
-        const uint64_t gid = (uint64_t)(v.env_base + slot);
-        act = (int)((uint32_t)(splitmix64(a.seed ^ (gid << 20) ^ (uint64_t)a.tick) >> 32) % 6u);
-      }
+      if (!a.actions) act = hashed_action(v, a.seed, slot, a.tick);
       asm volatile("" : "+v"(bc), "+v"(ref));                          // (no early wait on the flag)
       if (a.bc && (bc & 0xffu)) act = ref;                             // behaviour cloning, imitation.py:56-57
       s = unpack_state(st);
-      if (s.x < 1 || s.x > v.W - 2 || s.y < 1 || s.y > v.H - 2 || s.scen >= v.pool_count) {
+      if (!state_in_range(v, s)) {
         latch_error(v.err, CRAFT_EINVAL, slot);                          // never initialised
         live = false;
       }
@@ -217,45 +215,17 @@ __global__ __launch_bounds__(64 * TW + J * kTick2Tile * TL, CRAFT_T2_WPE) void t
     if (live) {
       // per-env body of ImitationTrainer.do_rollout, trainers/imitation.py:59-73
       bool restart = false;
-      if (s.frozen) {
-        d = 1;
-      } else {
-        counted = 1;
-        s.timer -= 1;
-        d = (act == CRAFT_STOP) || s.timer <= 0;
-        restart = d && (a.flags & CRAFT_STEP_AUTORESET);
-      }
-      if (d) {                                                           // satisfies() of the pre-step state
-        const uint32_t tt = s_task[s.task];
-        const int fc = (s.x + dir_dx(s.dir)) * v.H + (s.y + dir_dy(s.dir));
-        uint32_t mw = 0;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) mw |= (w == (fc >> 5)) ? m[w] : 0u;
-        const int goal = tt & 0xf, arg = (tt >> 4) & 0xff;
-        if (goal == CRAFT_GOAL_GET || goal == CRAFT_GOAL_MAKE) succ = iv[arg] > 0;
-        else if (goal == CRAFT_GOAL_GO) succ = (((mw >> (fc & 31)) & 1u) ? 0 : (int)g[fc]) == arg;
-        else succ = -1;
-      }
-      if (!restart) {
-#pragma unroll
-        for (int w = 0; w < 8; ++w) {                                    // cells cleared this episode
-          uint32_t mm = m[w];
-          while (mm) {
-            g[w * 32 + __ffs(mm) - 1] = 0;
-            mm &= mm - 1;
-          }
-        }
-      }
+      protocol_step(s, act, a.flags, d, counted, restart);
+      if (d) succ = satisfies_masked(v, g, iv, m, s, s_task[s.task]);    // of the pre-step state
+      if (!restart) apply_mask_to_row(m, g);                             // cells cleared this episode
       if (j == 0) T2S(-1, 3);
-      if (restart) {                                                     // CraftScenario.init, craft.py:268-273
-        s.x = init_word & 0xff; s.y = (init_word >> 8) & 0xff; s.dir = (init_word >> 16) & 3;
-        s.timer = v.maxT;
+      if (restart) {
+        restart_agent(s, init_word, v.maxT);
 #pragma unroll
         for (int w = 0; w < 8; ++w) { ivw[w] = 0u; m[w] = 0u; }
         inv_changed = mask_changed = true;
       } else if (d && !s.frozen) {
-        s.frozen = 1;
-        s.timer = max(s.timer, 0);
+        freeze_agent(s);
       } else if (!d) {
         if (act < 0 || act >= CRAFT_N_ACTIONS) {
           latch_error(v.err, CRAFT_EBADACTION, slot);
@@ -276,14 +246,12 @@ __global__ __launch_bounds__(64 * TW + J * kTick2Tile * TL, CRAFT_T2_WPE) void t
         v.mask[2 * slot] = make_uint4(m[0], m[1], m[2], m[3]);
         v.mask[2 * slot + 1] = make_uint4(m[4], m[5], m[6], m[7]);
       }
-      if (a.done) a.done[slot] = (uint8_t)d;
-      if (a.sat) a.sat[slot] = (int8_t)succ;
-      if (a.reward) a.reward[slot] = (counted && d && succ == 1) ? 1.0f : 0.0f;
+      store_outputs(a, slot, d, succ, counted);
       if (a.rec) a.rec[slot] = counted ? act : -1;                       // action_seqs, imitation.py:59-61
     }
     if (j == 0) T2S(-1, 5);
     if (a.code && lane < nE) a.code[slot] = (int8_t)code;
-    s_agent[le] = live ? ((uint32_t)s.x | ((uint32_t)s.y << 8) | ((uint32_t)s.dir << 16) | (1u << 24)) : 0u;
+    s_agent[le] = agent_word(s, live);
     // the teacher's inputs: task | frozen << 8 | scenario connected << 9 | the teacher table has
     // this grid (craft_teach.h) << 10 | its table row << 11 (< 2^21 when the table is on).  The row
     // holds this episode's clears (none after a restart): cleared listed cells read 0
@@ -296,16 +264,11 @@ __global__ __launch_bounds__(64 * TW + J * kTick2Tile * TL, CRAFT_T2_WPE) void t
                     (trow >= 0 ? (1u << 10) | ((uint32_t)trow << 11) : 0u);
     }
     // episode statistics: the partial-sum row of this 64-env tile (uncontended)
-    const uint64_t bs = __ballot(live && counted && d && succ == 1);
-    const uint64_t be = __ballot(live && counted && d);
-    const uint64_t bt = __ballot(live && counted);
+    uint32_t n_succ = 0, n_end = 0, n_step = 0;
+    tally_stats(live, counted, d, succ, n_succ, n_end, n_step);
     const uint64_t bl = __ballot(live && counted && !d);
-    if (lane == 0 && nE > 0) {   // no-return atomics
-      unsigned long long* r =
-          reinterpret_cast<unsigned long long*>(v.stats_part + 4 * ((int64_t)blockIdx.x * J + j));
-      atomicAdd(r + 0, (unsigned long long)__popcll(bs));
-      atomicAdd(r + 1, (unsigned long long)__popcll(be));
-      atomicAdd(r + 2, (unsigned long long)__popcll(bt));
+    if (lane == 0 && nE > 0) {
+      add_stats(v, (int64_t)blockIdx.x * J + j, n_succ, n_end, n_step);
       if (a.any_live && bl) *a.any_live = 1;                             // idempotent plain store
     }
     if (j == 0) T2S(2, 6);
@@ -379,10 +342,6 @@ __global__ __launch_bounds__(64 * TW + J * kTick2Tile * TL, CRAFT_T2_WPE) void t
       if (ag && ((ti >> 8) & 1u)) {
         action = -1;                                                     // frozen: the label of a done env
       } else if (ag) {
-#ifdef CRAFT_ABL_NOTEACH
-        action = CRAFT_STOP;                                             // ablation build only
-      } else if (false) {
-#endif
         Agent s{};
         s.x = ag & 0xff; s.y = (ag >> 8) & 0xff; s.dir = (ag >> 16) & 3; s.task = ti & 0xff;
         const uint32_t m0[8] = {0, 0, 0, 0, 0, 0, 0, 0};

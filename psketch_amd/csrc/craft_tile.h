@@ -17,6 +17,7 @@
 // The kernel is bound by E's HBM writes (F*4 = 1616 B per env at w=3).  See
 // DESIGN.md for the roofline and the phase timings that shaped this layout.
 #pragma once
+#include "craft_episode.h"
 #include "craft_obs.h"
 #include "craft_teach.h"
 
@@ -152,15 +153,12 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
         }
       } else {
         if (MODE == MODE_TICK) {
-          if (!a.actions) {
-            const uint64_t gid = (uint64_t)(v.env_base + slot);
-            act = (int)((uint32_t)(splitmix64(a.seed ^ (gid << 20) ^ (uint64_t)a.tick) >> 32) % 6u);
-          }
+          if (!a.actions) act = hashed_action(v, a.seed, slot, a.tick);
           asm volatile("" : "+v"(bc), "+v"(ref));                      // (no early wait on the flag)
           if (a.bc && (bc & 0xffu)) act = ref;                         // behaviour cloning, imitation.py:56-57
         }
         s = unpack_state(st);
-        if (s.x < 1 || s.x > v.W - 2 || s.y < 1 || s.y > v.H - 2 || s.scen >= v.pool_count) {
+        if (!state_in_range(v, s)) {
           latch_error(v.err, CRAFT_EINVAL, slot);   // never initialised by reset / set_state
           live = false;
         }
@@ -220,49 +218,21 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       bool restart = false;
       if (MODE == MODE_TICK) {
         // per-env body of ImitationTrainer.do_rollout, trainers/imitation.py:59-73
-        if (s.frozen) {
-          d = 1;
-        } else {
-          counted = 1;
-          s.timer -= 1;
-          d = (act == CRAFT_STOP) || s.timer <= 0;
-          restart = d && (a.flags & CRAFT_STEP_AUTORESET);
-        }
-        if (d) {
-          // satisfies() of the pre-step state: only the facing cell and the inventory matter
-          const uint32_t tt = s_task[s.task];
-          const int fc = (s.x + dir_dx(s.dir)) * v.H + (s.y + dir_dy(s.dir));
-          uint32_t mw = 0;
-#pragma unroll
-          for (int w = 0; w < 8; ++w) mw |= (w == (fc >> 5)) ? m[w] : 0u;
-          const int goal = tt & 0xf, arg = (tt >> 4) & 0xff;
-          if (goal == CRAFT_GOAL_GET || goal == CRAFT_GOAL_MAKE) succ = iv[arg] > 0;
-          else if (goal == CRAFT_GOAL_GO) succ = (((mw >> (fc & 31)) & 1u) ? 0 : (int)g[fc]) == arg;
-          else succ = -1;
-        }
+        protocol_step(s, act, a.flags, d, counted, restart);
+        // satisfies() of the pre-step state: only the facing cell and the inventory matter
+        if (d) succ = satisfies_masked(v, g, iv, m, s, s_task[s.task]);
       }
-      if (!restart) {
-#pragma unroll
-        for (int w = 0; w < 8; ++w) {                     // cells cleared this episode
-          uint32_t mm = m[w];
-          while (mm) {
-            g[w * 32 + __ffs(mm) - 1] = 0;
-            mm &= mm - 1;
-          }
-        }
-      }
+      if (!restart) apply_mask_to_row(m, g);              // cells cleared this episode
       if (MODE == MODE_RESET) {
         inv_changed = mask_changed = true;
       } else if (MODE == MODE_TICK) {
-        if (restart) {                                    // CraftScenario.init, craft.py:268-273
-          s.x = init_word & 0xff; s.y = (init_word >> 8) & 0xff; s.dir = (init_word >> 16) & 3;
-          s.timer = v.maxT;
+        if (restart) {
+          restart_agent(s, init_word, v.maxT);
 #pragma unroll
           for (int w = 0; w < 8; ++w) { ivw[w] = 0u; m[w] = 0u; }
           inv_changed = mask_changed = true;
         } else if (d && !s.frozen) {
-          s.frozen = 1;
-          s.timer = max(s.timer, 0);
+          freeze_agent(s);
         } else if (!d) {
           if (act < 0 || act >= CRAFT_N_ACTIONS) {
             latch_error(v.err, CRAFT_EBADACTION, slot);
@@ -306,14 +276,12 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       }
       if (MODE == MODE_TICK) {
         const int64_t i = env0 + tid;
-        if (a.done) a.done[i] = (uint8_t)d;
-        if (a.sat) a.sat[i] = (int8_t)succ;
-        if (a.reward) a.reward[i] = (counted && d && succ == 1) ? 1.0f : 0.0f;
+        store_outputs(a, i, d, succ, counted);
         if (a.rec) a.rec[i] = counted ? act : -1;        // action_seqs, imitation.py:59-61
       }
     }
     if ((MODE == MODE_TICK || MODE == MODE_TRANSITION) && a.code && tid < nE) a.code[env0 + tid] = (int8_t)code;
-    s_agent[tid] = live ? ((uint32_t)s.x | ((uint32_t)s.y << 8) | ((uint32_t)s.dir << 16) | (1u << 24)) : 0u;
+    s_agent[tid] = agent_word(s, live);
     // the teacher's inputs: task | frozen << 8 | scenario connected << 9 | the teacher table has
     // this grid (craft_teach.h) << 10 | its table row << 11 (< 2^21 when the table is on)
     if (TL > 0) {
@@ -326,15 +294,11 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
     }
     if (MODE == MODE_TICK) {
       // episode statistics: one partial-sum row per workgroup (uncontended)
-      const uint64_t bs = __ballot(live && counted && d && succ == 1);
-      const uint64_t be = __ballot(live && counted && d);
-      const uint64_t bt = __ballot(live && counted);
+      uint32_t n_succ = 0, n_end = 0, n_step = 0;
+      tally_stats(live, counted, d, succ, n_succ, n_end, n_step);
       const uint64_t bl = __ballot(live && counted && !d);
-      if (tid == 0) {   // no-return atomics: the wave does not wait for them
-        unsigned long long* r = reinterpret_cast<unsigned long long*>(v.stats_part + 4 * (int64_t)blockIdx.x);
-        atomicAdd(r + 0, (unsigned long long)__popcll(bs));
-        atomicAdd(r + 1, (unsigned long long)__popcll(be));
-        atomicAdd(r + 2, (unsigned long long)__popcll(bt));
+      if (tid == 0) {
+        add_stats(v, (int64_t)blockIdx.x, n_succ, n_end, n_step);
         if (a.any_live && bl) *a.any_live = 1;          // idempotent plain store
       }
     }
@@ -380,10 +344,6 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       if (ag && ((ti >> 8) & 1u)) {
         action = -1;                                      // frozen: the trainer's label for a done env
       } else if (ag) {
-#ifdef CRAFT_ABL_NOTEACH
-        action = CRAFT_STOP;                              // ablation build only: no teacher work
-      } else if (false) {
-#endif
         Agent s{};
         s.x = ag & 0xff; s.y = (ag >> 8) & 0xff; s.dir = (ag >> 16) & 3; s.task = ti & 0xff;
         const uint32_t m0[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -485,6 +485,136 @@ def test_multi_tick_rollout_equals_steps(world, W, tile, fmt, autoreset, given, 
     assert host(b.stats())[2] > 0
 
 
+_CLEARS_N, _CLEARS_T, _CLEARS_WOODS = 70, 30, 7      # one full 64-env tile plus a partial one
+_clears_cache = {}
+
+
+def _clears_case(world):
+    """A hand-made 12x12 scenario for the K-tick kernels' cleared-cell list: a boundary ring, seven
+    wood cells at (x, 5) for x = 2..8, every env at (1, 5) facing +x.  Env i repeats the script
+    [USE, RIGHT] x (i % 7), STOP under auto-reset, so it clears 0..6 cells per episode, restarts
+    and clears again (past three clears the list overflows and a restart restores the whole row).
+    Returns the inputs, the CPU variant's 30-tick rollout and a step-by-step GPU twin's, once per
+    world; nothing in it is modified by the tests."""
+    if world in _clears_cache:
+        return _clears_cache[world]
+    params, cb, tm, cfg = make_tables(world)
+    n, T = _CLEARS_N, _CLEARS_T
+    wood, boundary = cb.index["wood"], cb.index["boundary"]
+    grid = np.zeros((1, 12, 12), dtype=np.uint8)
+    grid[0, 0, :] = grid[0, -1, :] = grid[0, :, 0] = grid[0, :, -1] = boundary
+    grid[0, 2:2 + _CLEARS_WOODS, 5] = wood
+    task = tm["get[wood]"].id
+    specs = tuple(np.full(n, v, dtype=np.int32) for v in (0, 1, 5, N.RIGHT, task))
+    acts = np.empty((T, n), dtype=np.int32)
+    clears_now = np.empty(n, dtype=np.int64)             # USEs of the episode running after tick T - 1
+    for i in range(n):
+        script = [N.USE, N.RIGHT] * (i % 7) + [N.STOP]
+        acts[:, i] = [script[t % len(script)] for t in range(T)]
+        clears_now[i] = script[:T % len(script)].count(N.USE)
+
+    def outputs(sim, dev):
+        return {"obs": torch.zeros((T, n, sim.n_features), dtype=torch.float32, device=dev),
+                "reward": torch.zeros((T, n), dtype=torch.float32, device=dev),
+                "done": torch.zeros((T, n), dtype=torch.uint8, device=dev),
+                "success": torch.zeros((T, n), dtype=torch.int8, device=dev)}
+
+    def result(sim, out):
+        sim.check()
+        r = {k: host(t) for k, t in out.items()}
+        r.update({"state." + k: host(t) for k, t in sim.get_state().items()})
+        r["stats"] = host(sim.stats())
+        return r
+
+    cpu = CraftSim(world, n_envs=n, device="cpu", pool_capacity=1)
+    cpu.load_pool(grid)
+    cpu.reset(*specs)
+    out = outputs(cpu, "cpu")
+    cpu.rollout(T, actions=torch.as_tensor(acts), autoreset=True, **out)
+    ref_cpu = result(cpu, out)
+
+    twin = sim_with_pool(world, n, grid)
+    twin.reset(*specs)
+    out = outputs(twin, "cuda")
+    dacts = torch.as_tensor(acts, device="cuda")
+    cleared = np.zeros((T + 1, n), dtype=np.int64)       # cells cleared after tick t - 1
+    for t in range(T):
+        twin.step(dacts[t], tick=t, autoreset=True, obs=out["obs"][t], reward=out["reward"][t],
+                  done=out["done"][t], success=out["success"][t])
+        cleared[t + 1] = _CLEARS_WOODS - (host(twin.get_state(fields=("grid",))["grid"]) == wood).sum(1)
+    ref_steps = result(twin, out)
+    # not vacuous: some env restarts with five or more cleared cells, i.e. with an overflowed list
+    # that has taken further pushes (by construction every env with i % 7 >= 5)
+    restarts = ref_steps["done"].astype(bool)
+    assert (restarts & (cleared[:T] >= 5)).any()
+    for k in ref_cpu:
+        np.testing.assert_array_equal(ref_steps[k], ref_cpu[k], err_msg=k)
+    _clears_cache[world] = dict(grid=grid, specs=specs, acts=acts, wood=wood, clears_now=clears_now,
+                                outputs=outputs, result=result, ref_cpu=ref_cpu, ref_steps=ref_steps)
+    return _clears_cache[world]
+
+
+@pytest.mark.parametrize("world,tile,threads,chunk", [
+    ("craft_medium_12x12", 64, 256, 0),                  # rollout_kernel
+    ("craft_medium_12x12", 64, 512, 0),
+    ("craft_medium_12x12", 32, 256, 0),
+    ("craft_medium_12x12", 16, 128, 0),
+    ("craft_medium_12x12", 64, 256, 5),                  # units change hands mid-episode: the list rebuilt from the mask
+    ("craft_medium_12x12", 32, 512, 0),                  # rollout_split_kernel
+    ("craft_medium_12x12", 32, 512, -1),
+    ("craft_medium_12x12", 16, 320, 0),
+    ("craft_medium_12x12_w5", None, None, None)])        # the untuned default
+def test_rollout_restart_after_many_clears(world, tile, threads, chunk):
+    """An auto-reset after more clears than the cleared-cell list holds restores every cleared
+    cell: one craft_rollout launch of 30 ticks == 30 craft_step calls == the CPU variant
+    (observations, done / success / reward rings, get_state(), stats(), bit for bit), for every
+    K-tick kernel shape, and each env ends with seven wood cells minus its running episode's
+    clears.  (rollout_kernel's own push once dropped the list's overflow bit on the next clear:
+    built from that source, the five rollout_kernel cases and the 5x5 default failed with wrong
+    observations and grids, the three split-kernel cases passed.  ClearList::push in
+    craft_episode.h is now the only push.)"""
+    c = _clears_case(world)
+    sim = sim_with_pool(world, _CLEARS_N, c["grid"])
+    if tile is not None:
+        sim.tune(tile, 0, 1)
+        sim.tune_rollout(chunk, threads)
+    sim.reset(*c["specs"])
+    out = c["outputs"](sim, "cuda")
+    sim.rollout(_CLEARS_T, actions=torch.as_tensor(c["acts"], device="cuda"), autoreset=True, **out)
+    got = c["result"](sim, out)
+    for name, ref in (("steps", c["ref_steps"]), ("cpu", c["ref_cpu"])):
+        for k in ref:
+            np.testing.assert_array_equal(got[k], ref[k], err_msg=f"{k} vs {name}")
+    woods = (got["state.grid"] == c["wood"]).sum(1)
+    np.testing.assert_array_equal(woods, _CLEARS_WOODS - c["clears_now"])
+
+
+def test_rollout_teach_restart_after_many_clears():
+    """The same scenario and scripts through craft_rollout_teach (actions given, a label every
+    tick) against the CPU variant: the only K-tick kernel whose cleared-cell list also feeds the
+    label path."""
+    world = "craft_medium_12x12"
+    c = _clears_case(world)
+    n, T = _CLEARS_N, _CLEARS_T
+    res = []
+    for dev in ("cpu", "cuda"):
+        sim = CraftSim(world, n_envs=n, device="cpu" if dev == "cpu" else 0, pool_capacity=1)
+        sim.load_pool(c["grid"])
+        sim.reset(*c["specs"])
+        out = c["outputs"](sim, dev)
+        out["labels"] = torch.zeros((T, n), dtype=torch.int32, device=dev)
+        out["action_record"] = torch.zeros((T, n), dtype=torch.int32, device=dev)
+        sim.rollout_teach(T, actions=torch.as_tensor(c["acts"], device=dev), autoreset=True, **out)
+        res.append(c["result"](sim, out))
+    ref, got = res
+    for k in ref:
+        np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
+    for k in c["ref_cpu"]:                                # the ticks themselves: as craft_rollout's
+        np.testing.assert_array_equal(got[k], c["ref_cpu"][k], err_msg=k)
+    woods = (got["state.grid"] == c["wood"]).sum(1)
+    np.testing.assert_array_equal(woods, _CLEARS_WOODS - c["clears_now"])
+
+
 def test_empty_and_single_env_calls(gpu):
     """Zero-length calls are no-ops (no launch, no error); a one-env simulator
     runs every entry point."""
