@@ -340,6 +340,51 @@ int craft_host_flag_pointer(void* host, int32_t** device_out);
  * BFS overlaps the observation stores (config 5: a teacher label every tick). */
 int craft_step_teach(craft_sim_t* sim, const craft_step_args_t* args, int32_t* label_out, void* stream);
 
+/* One tick of the language trainers' rollout, in one launch: the per-env body of the loop the
+ * reference's PrimitiveLanguageTrainer, InteractivePrimitiveLanguageTrainer and
+ * ActivePrimitiveLanguageTrainer share (trainers/primitive_language.py:45-66,
+ * interactive_primitive_language.py:43-76, active_primitive_language.py:44-87), fused with
+ * features() of the new state and, with label_out, the DemonstrationTeacher on it.  Unlike
+ * craft_step's protocol the step comes first.  Per slot, in this order:
+ *   a slot frozen before the tick takes no step and leaves no record;
+ *   a = use_alt[i] ? alt_actions[i] : actions[i]   (the ASK bit, active_primitive_language.py:59-61);
+ *   an a outside 0..5 latches CRAFT_EBADACTION, and the slot stays as it is;
+ *   state = step(state, a)                          (STOP too: a no-op that keeps dir, code 5);
+ *   timer -= 1; done = (a == STOP) or timer <= 0;
+ *   a slot that ends freezes exactly as under craft_step: craft_step, craft_teacher and
+ *   craft_reset treat it as any frozen slot.
+ * Statistics go to craft_stats' counters: env-steps = slots that stepped, episodes ended = slots
+ * that ended this tick, successes = those that ended with satisfies() == 1.
+ * label_out (device int32[n_envs], NULL = no teacher in the launch) receives
+ * DemonstrationTeacher.__call__ of the new state of every slot not frozen before the tick, a
+ * slot whose episode this tick ended included (the reference keeps asking the teacher about done
+ * envs, interactive_primitive_language.py:49-50, and that state no longer changes); -1 for a
+ * slot frozen before the tick; -2 where the reference's teacher raises, which latches
+ * CRAFT_ETEACHER only for a slot still running after the tick (the reference asks about an
+ * ended env only while another env keeps its loop alive: the rollout layer decides).
+ * CRAFT_EINVAL: flags != 0, use_alt without alt_actions, or (with label_out) a launch under
+ * stream capture while pool rows wait for their teacher-table entries (craft_sim_sync_table).
+ * Always the one-tile kernel: of craft_sim_tune_teach's knobs, lanes and table apply. */
+typedef struct {
+  const int32_t* actions;       /* int32[n_envs], or NULL: the hashed draw (action_seed, tick) */
+  const int32_t* alt_actions;   /* int32[n_envs] or NULL */
+  const uint8_t* use_alt;       /* uint8[n_envs] or NULL: nonzero -> the slot acts on alt_actions[i] */
+  uint64_t action_seed;
+  int64_t  tick;
+  uint32_t flags;               /* must be 0: no auto-reset in this protocol */
+  void*    obs;                 /* [n_envs][n_features], handle's obs format: features() of every
+                                   slot's state after the tick (a frozen slot: its final state) */
+  uint8_t* done;                /* 1 for a slot that is done after this tick (ended now or before) */
+  int8_t*  success;             /* done slots: satisfies(own task) of the current state,
+                                   1 / 0 / -1 (None); running slots: -1 */
+  int32_t* action_record;       /* the action stepped, -1 for a slot done before the tick */
+  int8_t*  ask_record;          /* use_alt bit of a slot that stepped, -1 otherwise */
+  int8_t*  transition_code;     /* craft_transition's codes; -1 for a slot done before the tick */
+  int32_t* any_live;            /* as craft_step_ex */
+  int32_t* label_out;           /* NULL = no teacher in the launch */
+} craft_lang_step_args_t;
+int craft_step_lang(craft_sim_t* sim, const craft_lang_step_args_t* args, void* stream);
+
 /* n_ticks consecutive craft_step ticks (tick0, tick0+1, ...) in one launch, with
  * results identical to n_ticks craft_step calls: each workgroup keeps its envs
  * on chip between ticks, so the per-tick prologue overlaps other workgroups'

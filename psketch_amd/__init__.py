@@ -11,8 +11,9 @@ from .sim import CraftSim, hash_actions, sample_scenarios, splitmix64, synthetic
 from .dataset import Dataset
 from .rollout import ImitationRollout, RolloutInfo, do_rollout
 from .language import PrimitiveLanguageTeacher
+from .language_rollout import LanguageRolloutInfo, do_language_rollout
 
 __all__ = ["gamedef", "Cookbook", "Index", "Task", "TaskManager", "compile_config",
            "world_params", "CraftSim", "hash_actions", "sample_scenarios", "splitmix64",
            "synthetic_specs", "Dataset", "ImitationRollout", "RolloutInfo", "do_rollout",
-           "PrimitiveLanguageTeacher"]
+           "PrimitiveLanguageTeacher", "LanguageRolloutInfo", "do_language_rollout"]

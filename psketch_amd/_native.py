@@ -97,6 +97,25 @@ class craft_step_args_t(ctypes.Structure):
     ]
 
 
+class craft_lang_step_args_t(ctypes.Structure):
+    _fields_ = [
+        ("actions", ctypes.c_void_p),
+        ("alt_actions", ctypes.c_void_p),
+        ("use_alt", ctypes.c_void_p),
+        ("action_seed", ctypes.c_uint64),
+        ("tick", ctypes.c_int64),
+        ("flags", ctypes.c_uint32),
+        ("obs", ctypes.c_void_p),
+        ("done", ctypes.c_void_p),
+        ("success", ctypes.c_void_p),
+        ("action_record", ctypes.c_void_p),
+        ("ask_record", ctypes.c_void_p),
+        ("transition_code", ctypes.c_void_p),
+        ("any_live", ctypes.c_void_p),
+        ("label_out", ctypes.c_void_p),
+    ]
+
+
 class craft_rollout_teach_args_t(ctypes.Structure):
     _fields_ = [
         ("actions", ctypes.c_void_p),
@@ -156,6 +175,7 @@ SIGNATURES = {
     "craft_step": (_i32, [_vp, _vp, _u64, _i64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "craft_step_ex": (_i32, [_vp, ctypes.POINTER(craft_step_args_t), _vp]),
     "craft_step_teach": (_i32, [_vp, ctypes.POINTER(craft_step_args_t), _vp, _vp]),
+    "craft_step_lang": (_i32, [_vp, ctypes.POINTER(craft_lang_step_args_t), _vp]),
     "craft_rollout": (_i32, [_vp, _vp, _u64, _i64, _i32, _u32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "craft_rollout_teach": (_i32, [_vp, ctypes.POINTER(craft_rollout_teach_args_t), _vp]),
     "craft_stats": (_i32, [_vp, _vp, _i32, _vp]),

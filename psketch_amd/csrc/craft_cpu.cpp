@@ -950,6 +950,98 @@ int craft_step_teach(craft_sim_t* s, const craft_step_args_t* x, int32_t* label_
   return run_ticks(s, in, x->any_live);
 }
 
+// One tick of the language trainers' loop (trainers/primitive_language.py:45-66 and its
+// interactive / active variants) for every slot: step first, then the timer and done, success
+// read off the new state, the teacher on every slot that was running before the tick.
+int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* /*stream*/) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (x->flags != 0) return fail(s, CRAFT_EINVAL, "craft_step_lang: flags must be 0 (no auto-reset in this protocol)");
+  if (x->use_alt && !x->alt_actions) return fail(s, CRAFT_EINVAL, "craft_step_lang: use_alt needs alt_actions");
+  if (x->obs && (reinterpret_cast<uintptr_t>(x->obs) & 15u))
+    return fail(s, CRAFT_EINVAL, "craft_step_lang: obs must be 16-byte aligned");
+  if (x->label_out && 4 * s->C > 1000)
+    return fail(s, CRAFT_EINVAL, "craft_step_lang: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  std::atomic<int64_t> n_succ{0}, n_ended{0}, n_steps{0};
+  std::atomic<bool> running{false};
+  parallel_for(s, s->n_envs, [&](int64_t lo, int64_t hi) {
+    int64_t succs = 0, ended = 0, steps = 0;
+    bool some_running = false;
+    std::vector<uint8_t> g(CRAFT_MAX_CELLS), row(s->F);
+    for (int64_t i = lo; i < hi; ++i) {
+      Agent a = unpack_state(s->state[i]);
+      const bool valid = a.x >= 1 && a.x <= s->W - 2 && a.y >= 1 && a.y <= s->H - 2 && a.scen < s->pool_count;
+      if (!valid) {                                    // never initialised by reset / set_state
+        latch(s, CRAFT_EINVAL, i);
+        if (x->transition_code) x->transition_code[i] = -1;
+        if (x->obs) {
+          std::memset(row.data(), 0, s->F);
+          put_obs(s->obs_fmt, x->obs, i, s->F, row.data());
+        }
+        if (x->label_out) x->label_out[i] = -2;
+        continue;
+      }
+      uint8_t* iv = s->inv.data() + 32 * i;
+      env_grid(s, i, a.scen, g.data());
+      const bool done_before = a.frozen != 0;
+      bool stepped = false, asked = false;
+      int action = -1, code = -1;
+      if (!done_before) {
+        asked = x->use_alt && x->use_alt[i];
+        if (asked) action = x->alt_actions[i];
+        else if (x->actions) action = x->actions[i];
+        else action = (int)((uint32_t)(splitmix64(x->action_seed ^ ((uint64_t)(s->env_base + i) << 20) ^
+                                                  (uint64_t)x->tick) >> 32) % 6u);
+        if (action < 0 || action >= CRAFT_N_ACTIONS) {
+          latch(s, CRAFT_EBADACTION, i);
+        } else {
+          const int ox = a.x, oy = a.y;
+          bool ic = false, mc = false;
+          transition(s, g.data(), iv, a, s->mask.data() + 8 * i, action, ic, mc, i);
+          code = transition_code(ox, oy, a, ic);
+          stepped = true;
+          a.timer -= 1;
+          if (action == CRAFT_STOP || a.timer <= 0) {
+            a.frozen = 1;
+            if (a.timer < 0) a.timer = 0;
+          }
+          s->state[i] = pack_state(a);
+        }
+      }
+      const bool done_now = a.frozen != 0;
+      const int sat = done_now ? satisfies(s, g.data(), iv, a, a.task) : -1;
+      if (x->done) x->done[i] = done_now ? 1 : 0;
+      if (x->success) x->success[i] = (int8_t)sat;
+      if (x->action_record) x->action_record[i] = stepped ? action : -1;
+      if (x->ask_record) x->ask_record[i] = (int8_t)(stepped ? (asked ? 1 : 0) : -1);
+      if (x->transition_code) x->transition_code[i] = (int8_t)code;
+      steps += stepped;
+      ended += stepped && done_now;
+      succs += stepped && done_now && sat == 1;
+      some_running = some_running || (stepped && !done_now);
+      if (x->obs) {
+        features(s, g.data(), iv, a, row.data());
+        put_obs(s->obs_fmt, x->obs, i, s->F, row.data());
+      }
+      if (x->label_out) {
+        int label = -1;                                // done before the tick
+        if (!done_before) {
+          int len = -1, err = 0;
+          label = teach(s, g.data(), iv, a, a.task, false, len, err);
+          if (err && !done_now) latch(s, err, i);      // an env that just ended: the rollout layer's call
+        }
+        x->label_out[i] = label;
+      }
+    }
+    n_succ += succs; n_ended += ended; n_steps += steps;
+    if (some_running) running = true;
+  });
+  s->stats[0] += n_succ.load();
+  s->stats[1] += n_ended.load();
+  s->stats[2] += n_steps.load();
+  if (x->any_live && running.load()) *x->any_live = 1;
+  return CRAFT_OK;
+}
+
 int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, int64_t tick0, int32_t n_ticks,
                   uint32_t flags, void* obs, int32_t ring, float* reward, uint8_t* done, int8_t* success,
                   void* /*stream*/) {

@@ -30,7 +30,8 @@ constexpr int kMaxTileEnvs = 64;   // envs per workgroup tile: 16, 32 or 64
 constexpr int kMinTileEnvs = 16;
 constexpr int kInvStride = 36;     // LDS bytes per inventory row (9 dwords: bank-spread)
 
-enum Mode { MODE_TICK = 0, MODE_TRANSITION = 1, MODE_OBSERVE = 2, MODE_RESET = 3 };
+// MODE_LANG: the language trainers' tick (craft_step_lang): step first, then the timer
+enum Mode { MODE_TICK = 0, MODE_TRANSITION = 1, MODE_OBSERVE = 2, MODE_RESET = 3, MODE_LANG = 4 };
 
 struct SimView {
   const uint8_t* pool;
@@ -212,12 +213,13 @@ struct TileArgs {
   float* reward;
   uint8_t* done;
   int8_t* sat;
-  const int32_t* ref;      // MODE_TICK rollout fusion (craft_step_ex)
+  const int32_t* ref;      // MODE_TICK rollout fusion (craft_step_ex); MODE_LANG: alt_actions / use_alt
   const uint8_t* bc;
   int32_t* rec;
   int32_t* any_live;
   int8_t* code;            // transition codes (craft_step_ex, craft_transition)
   int32_t* label;          // craft_step_teach: teacher label of every env's new state
+  int8_t* ask;             // MODE_LANG: the use_alt bit of a slot that stepped, else -1
 };
 
 struct RolloutArgs {       // craft_rollout: n_ticks ticks in one launch

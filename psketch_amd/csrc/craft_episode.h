@@ -1,6 +1,7 @@
 // craft_episode.h — the one definition of what every tick kernel must agree on: the per-env
-// body of ImitationTrainer.do_rollout (trainers/imitation.py:59-73) in pieces, and the K-tick
-// kernels' cleared-cell bookkeeping.
+// body of ImitationTrainer.do_rollout (trainers/imitation.py:59-73) in pieces, the language
+// trainers' variant of it (tile_kernel's MODE_LANG), and the K-tick kernels' cleared-cell
+// bookkeeping.
 //
 // Everything here is __device__ __forceinline__, works on state passed by reference, touches
 // no LDS of its own and has no barrier, so a kernel keeps its own scheduling (wave roles,
@@ -42,6 +43,30 @@ __device__ __forceinline__ void protocol_step(Agent& s, const int& act, const ui
     s.timer -= 1;
     d = (act == CRAFT_STOP) || s.timer <= 0;
     restart = d && (flags & CRAFT_STEP_AUTORESET);
+  }
+}
+
+// The language trainers' tick (trainers/primitive_language.py:45-66, interactive_primitive_
+// language.py:43-76, active_primitive_language.py:44-87; craft_step_lang), in two pieces around
+// the caller's CraftState.step.  Before it: a frozen env is done and leaves no record; a running
+// one steps whatever its action (STOP too), unless the action is none of the six (bad: the
+// caller latches CRAFT_EBADACTION and the slot stays as it is).
+__device__ __forceinline__ void language_step_begin(const Agent& s, const int& act, int& d, int& counted, bool& bad) {
+  if (s.frozen) {
+    d = 1;
+  } else {
+    bad = act < 0 || act >= CRAFT_N_ACTIONS;
+    counted = !bad;
+  }
+}
+// After it: only now the timer drops and done latches (the env freezes as under craft_step);
+// the caller reads satisfies() off the state the step left.
+__device__ __forceinline__ void language_step_end(Agent& s, const int& act, int& d) {
+  s.timer -= 1;
+  d = (act == CRAFT_STOP) || s.timer <= 0;
+  if (d) {
+    s.frozen = 1;
+    s.timer = max(s.timer, 0);
   }
 }
 

@@ -1,7 +1,8 @@
 // craft_sim.hip — host side of the C ABI (include/craft.h): handle lifetime,
 // scenario pool, launches, state I/O and episode statistics.
-// Kernels: craft_tile.hip (tick / transition / observe / reset), craft_rollout.hip
-// (multi-tick), craft_teacher.hip, craft_scenarios.hip (pool generation).
+// Kernels: craft_tile.hip (tick / transition / observe / reset), craft_tick_lang.hip (the
+// language trainers' tick), craft_rollout.hip (multi-tick), craft_teacher.hip,
+// craft_scenarios.hip (pool generation).
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -27,6 +28,8 @@ hipError_t launch_scenarios(const SimView& v, const ScenarioArgs& a, hipStream_t
 hipError_t launch_tick_teach(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
                              hipStream_t st);
 hipError_t launch_tick2(int tl, int nw, const SimView& v, const TileArgs& a, size_t lds, hipStream_t st);
+hipError_t launch_tick_lang(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
+                            hipStream_t st);
 size_t tick2_lds_bytes(int tl, int nw, int GS, int F);
 hipError_t launch_teach_table(int nw, const SimView& v, int32_t first, int32_t count, const int32_t* kinds,
                               hipStream_t st);
@@ -264,6 +267,13 @@ int teach_tile(const craft_sim* s) {
   return s->cfg.window_width == 3 || s->tile != 32 ? craft::kMaxTileEnvs : 32;
 }
 
+// Teacher lanes per env of the one-tile kernel (craft_sim_tune_teach): quads, or pairs on the
+// 32-env tile of wider windows (76.5 against 78.5 us with quads at 5x5), or what the knob says.
+int one_tile_lanes(const craft_sim* s) {
+  return (s->teach_lanes == 1 || s->teach_lanes == 2) ? s->teach_lanes
+         : s->teach_lanes == 0 && teach_tile(s) == 32 ? 2 : 4;
+}
+
 // What craft_step / craft_step_ex (teach = false) or craft_step_teach (teach = true) launches:
 // CRAFT_KERNEL_TILE (craft_tile.h) or CRAFT_KERNEL_TICK2 (craft_tick2.h), with its envs per
 // tile / workgroup and teacher lanes per env.
@@ -283,9 +293,7 @@ void step_shape(const craft_sim* s, bool teach, int* kernel, int* envs, int* lan
   // teacher lanes per env (craft_sim_tune_teach): the two-tile kernel runs pairs (or quads), the
   // one-tile kernel quads (or pairs, or one lane)
   const int tl2 = s->teach_lanes == 4 ? 4 : 2;
-  // (the 32-env tile of wider windows: pairs by default, 76.5 against 78.5 us with quads at 5x5)
-  const int tl1 = (s->teach_lanes == 1 || s->teach_lanes == 2) ? s->teach_lanes
-                  : s->teach_lanes == 0 && teach_tile(s) == 32 ? 2 : 4;
+  const int tl1 = one_tile_lanes(s);
   if (k == 2) { *kernel = 2; *envs = 128; *lanes = tl2; }
   else { *kernel = 1; *envs = teach_tile(s); *lanes = tl1; }
 }
@@ -904,6 +912,48 @@ int craft_step_teach(craft_sim_t* s, const craft_step_args_t* x, int32_t* label_
     e = craft::launch_tick_teach(tl, nw, s->cfg.window_width, tile, v, a, lds, st);
   }
   if (e != hipSuccess) return hip_fail(s, e, "craft_step_teach launch");
+  return CRAFT_OK;
+}
+
+int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (x->flags != 0) return fail(s, CRAFT_EINVAL, "craft_step_lang: flags must be 0 (no auto-reset in this protocol)");
+  if (x->use_alt && !x->alt_actions) return fail(s, CRAFT_EINVAL, "craft_step_lang: use_alt needs alt_actions");
+  if (x->obs && !aligned16(x->obs)) return fail(s, CRAFT_EINVAL, "craft_step_lang: obs must be 16-byte aligned");
+  if (x->label_out && 4 * s->view.C > 1000)
+    return fail(s, CRAFT_EINVAL, "craft_step_lang: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  TileArgs a{};
+  a.actions = x->actions;
+  a.ref = x->alt_actions;
+  a.bc = x->use_alt;
+  a.seed = x->action_seed;
+  a.tick = x->tick;
+  a.n = s->n_envs;
+  a.obs = x->obs;
+  a.done = x->done;
+  a.sat = x->success;
+  a.rec = x->action_record;
+  a.ask = x->ask_record;
+  a.code = x->transition_code;
+  a.any_live = x->any_live;
+  a.label = x->label_out;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipError_t e;
+  if (!x->label_out) {
+    e = craft::launch_tick_lang(0, 0, s->cfg.window_width, s->tile, s->view, a, tile_lds_bytes(s, s->tile), st);
+  } else {
+    const int frc = flush_table(s, stream, "craft_step_lang");
+    if (frc != CRAFT_OK) return frc;
+    SimView v = teach_view(s);
+    v.tt_fused = s->teach_table != 2;
+    // the one-tile kernel in craft_step_teach's shape: its tile, its lanes, its LDS
+    const int tile = teach_tile(s);
+    const size_t lds = (size_t)craft::lds_layout(tile, s->view.GS, s->view.F).bytes +
+                       (((size_t)s->view.n_tasks * CRAFT_MAX_SUBTASKS + 15) & ~size_t(15));
+    e = craft::launch_tick_lang(one_tile_lanes(s), craft::teach_words(s->view.W, s->view.H), s->cfg.window_width, tile,
+                                v, a, lds, st);
+  }
+  if (e != hipSuccess) return hip_fail(s, e, "craft_step_lang launch");
   return CRAFT_OK;
 }
 

@@ -751,7 +751,9 @@ __device__ __forceinline__ int teach_env(const SimView& v, const uint16_t* task_
 // instructions on envs that need one instead of on the few of its own.  grid / agent / info as the fused kernels keep them in LDS (info: task |
 // frozen << 8 | connected << 9); label: the label row of the workgroup's first env; ws / is: the
 // word strides of work and info (1: arrays; the one-tile kernel keeps them in row padding).
-template <int NW, int LANES>
+// ENDED: bit 25 of an agent word marks an env whose episode this tick ended (craft_step_lang): it
+// gets its label (-2 where the reference raises) without latching the error.
+template <int NW, int LANES, bool ENDED = false>
 __device__ __forceinline__ void teach_deferred(const SimView& v, const uint32_t* work, int n, int g, int G, int ql,
                                                const uint8_t* s_grid, int GS, const uint32_t* s_agent,
                                                const uint32_t* s_info, int32_t* label, int64_t env0, int ws = 1,
@@ -772,7 +774,7 @@ __device__ __forceinline__ void teach_deferred(const SimView& v, const uint32_t*
                                            ((ti >> 9) & 1u) != 0);
     const int action = go_leaf_action(ok, fa, len, err);
     if (ql == 0) {
-      if (err) latch_error(v.err, err, env0 + e);
+      if (err && !(ENDED && ((ag >> 25) & 1u))) latch_error(v.err, err, env0 + e);
       label[e] = action;
     }
   }
@@ -781,15 +783,15 @@ __device__ __forceinline__ void teach_deferred(const SimView& v, const uint32_t*
 // The dense pass over NT teacher threads (thread u of them) with the widest lane groups the count
 // allows: quads, the BFS's shortest dependent chain, when the n queries fit one per quad, else
 // the kernel's own LANES (n is workgroup-uniform, so is the branch).
-template <int NW, int LANES>
+template <int NW, int LANES, bool ENDED = false>
 __device__ __forceinline__ void teach_deferred_dense(const SimView& v, const uint32_t* work, int n, int u, int NT,
                                                      const uint8_t* s_grid, int GS, const uint32_t* s_agent,
                                                      const uint32_t* s_info, int32_t* label, int64_t env0,
                                                      int ws = 1, int is = 1) {
   if (LANES < 4 && n <= NT / 4)
-    teach_deferred<NW, 4>(v, work, n, u >> 2, NT / 4, u & 3, s_grid, GS, s_agent, s_info, label, env0, ws, is);
+    teach_deferred<NW, 4, ENDED>(v, work, n, u >> 2, NT / 4, u & 3, s_grid, GS, s_agent, s_info, label, env0, ws, is);
   else
-    teach_deferred<NW, LANES>(v, work, n, u / LANES, NT / LANES, u % LANES, s_grid, GS, s_agent, s_info, label, env0,
+    teach_deferred<NW, LANES, ENDED>(v, work, n, u / LANES, NT / LANES, u % LANES, s_grid, GS, s_agent, s_info, label, env0,
                               ws, is);
 }
 

@@ -23,7 +23,10 @@
 
 namespace craft {
 
-// TL > 0 (MODE_TICK only): TILE * TL more threads run the DemonstrationTeacher on
+// MODE_LANG (craft_step_lang) is the tick of the language trainers' protocol: the same phases,
+// with the step before the timer and satisfies() read off the new state (craft_episode.h).
+//
+// TL > 0 (MODE_TICK and MODE_LANG only): TILE * TL more threads run the DemonstrationTeacher on
 // every env's new state (craft_step_teach), TL lanes per env, while the first
 // tick threads stream the observations: the BFS reads the grid rows the tick left in
 // LDS.  NW = 32-bit words per cell set (teach_env).
@@ -74,6 +77,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
   const int nE = (int)min((int64_t)TILE, a.n - env0);
   const bool want_obs = a.obs != nullptr;
   const int F = v.F;
+  constexpr bool kTick = MODE == MODE_TICK || MODE == MODE_LANG;   // a rollout tick of either protocol
 
   STAMP(0);
   // ---- A + C: wave 0, one lane per env ------------------------------------------------------
@@ -105,8 +109,9 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       m0 = v.mask[2 * slot];
       m1 = v.mask[2 * slot + 1];
       if (MODE == MODE_TICK || MODE == MODE_TRANSITION) init_word = v.init[slot];
-      if (MODE == MODE_TICK) {
+      if (kTick) {
         if (a.actions) act = a.actions[slot];
+        // (MODE_LANG: use_alt and alt_actions, the same two loads in the same batch)
         if (a.bc) {
           bc = a.bc[slot];
           ref = a.ref[slot];
@@ -152,10 +157,12 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
           s.x = x0; s.y = y0; s.dir = d0; s.frozen = 0; s.timer = v.maxT; s.scen = sc; s.task = tk;
         }
       } else {
-        if (MODE == MODE_TICK) {
+        if (kTick) {
           if (!a.actions) act = hashed_action(v, a.seed, slot, a.tick);
           asm volatile("" : "+v"(bc), "+v"(ref));                      // (no early wait on the flag)
-          if (a.bc && (bc & 0xffu)) act = ref;                         // behaviour cloning, imitation.py:56-57
+          // behaviour cloning, imitation.py:56-57; MODE_LANG: the ASK bit's candidate action,
+          // active_primitive_language.py:59-61
+          if (a.bc && (bc & 0xffu)) act = ref;
         }
         s = unpack_state(st);
         if (!state_in_range(v, s)) {
@@ -212,6 +219,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
     bool inv_changed = false, mask_changed = false;
     int d = 0, succ = -1, counted = 0;
     int code = -1;                                         // transition code (craft.h)
+    int was_frozen = 0;                                    // MODE_LANG: frozen before the tick
     if (live) {
       // The LDS row holds pool[scenario]; cells cleared this episode are applied
       // lazily, so an auto-reset (which restores exactly that row) needs no reload.
@@ -242,6 +250,20 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
             code = transition_code(ox, oy, s, inv_changed);
           }
         }
+      } else if (MODE == MODE_LANG) {
+        // per-env body of the language trainers' loop, trainers/primitive_language.py:45-66
+        bool bad = false;
+        was_frozen = s.frozen;
+        language_step_begin(s, act, d, counted, bad);
+        if (bad) latch_error(v.err, CRAFT_EBADACTION, slot);
+        if (counted) {
+          const int ox = s.x, oy = s.y;
+          transition<TILE == 64>(v, s_rc, g, iv, s, m, act, inv_changed, mask_changed, rw[0], slot);
+          code = transition_code(ox, oy, s, inv_changed);
+          language_step_end(s, act, d);
+        }
+        // satisfies() of the state the step left (a slot frozen before: its final state)
+        if (d) succ = satisfies(v, g, iv, s, s_task[s.task]);
       } else if (MODE == MODE_TRANSITION) {
         if (act >= CRAFT_N_ACTIONS) {
           latch_error(v.err, CRAFT_EBADACTION, slot);
@@ -274,25 +296,29 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
         v.mask[2 * dslot] = make_uint4(m[0], m[1], m[2], m[3]);
         v.mask[2 * dslot + 1] = make_uint4(m[4], m[5], m[6], m[7]);
       }
-      if (MODE == MODE_TICK) {
+      if (kTick) {
         const int64_t i = env0 + tid;
         store_outputs(a, i, d, succ, counted);
         if (a.rec) a.rec[i] = counted ? act : -1;        // action_seqs, imitation.py:59-61
+        if (MODE == MODE_LANG && a.ask) a.ask[i] = (int8_t)(counted ? (a.bc && (bc & 0xffu)) : -1);
       }
     }
-    if ((MODE == MODE_TICK || MODE == MODE_TRANSITION) && a.code && tid < nE) a.code[env0 + tid] = (int8_t)code;
-    s_agent[tid] = agent_word(s, live);
-    // the teacher's inputs: task | frozen << 8 | scenario connected << 9 | the teacher table has
+    if ((kTick || MODE == MODE_TRANSITION) && a.code && tid < nE) a.code[env0 + tid] = (int8_t)code;
+    // (MODE_LANG, bit 25: the episode ended this tick; the teacher still labels the slot, but what
+    // the reference's teacher would raise there is the rollout layer's to report)
+    s_agent[tid] = agent_word(s, live) | ((MODE == MODE_LANG && live && counted && d) ? (1u << 25) : 0u);
+    // the teacher's inputs: task | frozen << 8 (MODE_LANG: frozen before the tick, so a slot that
+    // just ended is still labelled) | scenario connected << 9 | the teacher table has
     // this grid (craft_teach.h) << 10 | its table row << 11 (< 2^21 when the table is on)
     if (TL > 0) {
       int ncl = 0;
 #pragma unroll
       for (int w = 0; w < 8; ++w) ncl += __popc(m[w]);
       const int trow = live ? tt_index(v, s.scen, tcw0, tcw1, ncl, [&](int c) { return g[c] == 0; }) : -1;
-      s_tinfo[tid * tis] = (uint32_t)s.task | ((uint32_t)s.frozen << 8) | (conn << 9) |
+      s_tinfo[tid * tis] = (uint32_t)s.task | ((uint32_t)(MODE == MODE_LANG ? was_frozen : s.frozen) << 8) | (conn << 9) |
                      (trow >= 0 ? (1u << 10) | ((uint32_t)trow << 11) : 0u);
     }
-    if (MODE == MODE_TICK) {
+    if (kTick) {
       // episode statistics: one partial-sum row per workgroup (uncontended)
       uint32_t n_succ = 0, n_end = 0, n_step = 0;
       tally_stats(live, counted, d, succ, n_succ, n_end, n_step);
@@ -354,7 +380,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
                                    m0, s_inv + e * kInvStride, s, s.task, ql, false, len, err,
                                    ((ti >> 9) & 1u) != 0, (v.tt_fused && ((ti >> 10) & 1u)) ? tt_row(v, (int)(ti >> 11)) : nullptr,
                                    &defer, (v.tt_fused && ((ti >> 10) & 1u)) ? tt_row4(v, (int)(ti >> 11)) : nullptr);
-        if (err && ql == 0) latch_error(v.err, err, i);
+        if (err && ql == 0 && !(MODE == MODE_LANG && ((ag >> 25) & 1u))) latch_error(v.err, err, i);
         if (action == kTeachDeferred && ql == 0)
           s_work[kWs * __hip_atomic_fetch_add(&s_wctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)] =
               (uint32_t)e | ((uint32_t)defer << 8);
@@ -364,15 +390,16 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
     // every teacher wave has listed its deferred queries; then all of them run the BFS densely
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     if ((tid & 63) == 0) __hip_atomic_fetch_add(&s_wctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (__hip_atomic_load(&s_wctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < (uint32_t)(TILE * TL / 64))
+    // (the number of teacher waves: a 32-env tile with one lane per env still has one)
+    while (__hip_atomic_load(&s_wctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < (uint32_t)((TILE * TL + 63) / 64))
       __builtin_amdgcn_s_sleep(1);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     const uint32_t nw = __hip_atomic_load(&s_wctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #ifdef CRAFT_STAMPS_TT      // diagnostic: 1 the teacher's walks done, 2 its dense pass done, 4 E done
     if (tid == NT && v.stamps) v.stamps[8 * (int64_t)blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
 #endif
-    teach_deferred_dense<NW, TL>(v, s_work, (int)nw, u, TILE * TL, s_grid, v.GS, s_agent, s_tinfo, a.label + env0,
-                                 env0, kWs, tis);
+    teach_deferred_dense<NW, TL, MODE == MODE_LANG>(v, s_work, (int)nw, u, TILE * TL, s_grid, v.GS, s_agent, s_tinfo,
+                                                    a.label + env0, env0, kWs, tis);
 #ifdef CRAFT_STAMPS_TT
     STAMP_MAX(2);
 #endif

@@ -1,0 +1,272 @@
+"""Batched do_rollout of the reference's three language trainers
+(trainers/primitive_language.py:16-143, interactive_primitive_language.py:16-106,
+active_primitive_language.py:16-119) on CraftSim slots.
+
+Their shared loop differs from ImitationTrainer.do_rollout in the tick itself: every running
+env steps first (STOP too), only then its timer drops and done latches, and success is
+satisfies() of the final state.  One craft_step_lang launch (include/craft.h) is that tick for
+the whole batch: the step, the protocol bookkeeping, the action / ASK records, the transition
+codes PrimitiveLanguageTeacher.describe reads, features() of the new states, the any-live flag
+and, when training, the DemonstrationTeacher's label of every new state (the next tick's
+instruction).  Per tick the host runs the student's calls, that launch and one read of the
+any-live flag (rollout.py's mapped flags); describe() learns the student's action -> word map
+sequentially on the host from one action and one code per env.  The summary is
+craft_rollout_distances, as for do_rollout.
+
+The student is duck-typed after the reference's students, batched (INTEGRATION.md has the
+signatures); `teacher` is a language.PrimitiveLanguageTeacher, whose student_action_map and
+draws from the shared RandomState come out as the reference's.
+"""
+import numpy as np
+import torch
+
+from . import _native as N
+from .language import WORDS
+from .rollout import RolloutError, _live_flags
+
+MODES = ("primitive", "interactive", "active")
+PAD = "<PAD>"
+ASK = 1            # students/active_primitive_language.py:17
+
+
+class LanguageRolloutInfo:
+    """The rollout's `info` as tensors: action_seqs int32 [T, n] (-1 where the env did not
+    act), n_actions int32 [n], success int8 [n] (1 / 0 / -1 for None), distances int32 [n]
+    (-1 where the task is not a get task), is_get bool [n], num_interactions, num_steps,
+    ticks (of the last pass)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def as_info(self):
+        """The reference's info dict (python lists; success keeps None)."""
+        A = self.action_seqs.t().cpu().numpy()
+        L = self.n_actions.cpu().numpy()
+        succ = self.success.cpu().numpy()
+        dist = self.distances.cpu().numpy()
+        is_get = self.is_get.cpu().numpy()
+        return {
+            "action_seqs": [[int(a) for a in A[i, :L[i]]] for i in range(len(L))],
+            "success": [None if s < 0 else bool(s) for s in succ],
+            "distances": [int(d) for d, g in zip(dist, is_get) if g],
+            "num_interactions": int(self.num_interactions),
+            "num_steps": int(self.num_steps),
+        }
+
+
+def _actions(a, n, dev):
+    if not torch.is_tensor(a):
+        a = torch.as_tensor(np.asarray(a), device=dev)
+    return a.to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+
+
+class _Pass:
+    """One pass of the loop `while not all(done)` from the episodes' initial states: the
+    buffers of its ticks and the tick itself."""
+
+    def __init__(self, sim, spec, teach):
+        n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
+        self.sim, self.n, self.T = sim, n, T
+        self.obs = sim.empty_obs()
+        sim.reset(*spec, obs=self.obs)
+        self.seqs = torch.full((T, n), -1, dtype=torch.int32, device=dev)
+        self.asks = torch.full((T, n), -1, dtype=torch.int8, device=dev)
+        self.codes = torch.full((T, n), -1, dtype=torch.int8, device=dev)
+        self.done = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.success = torch.full((n,), -1, dtype=torch.int8, device=dev)
+        self.new_labels = torch.empty(n, dtype=torch.int32, device=dev) if teach else None
+        self.ticks = 0
+        if sim._cpu:
+            self.flags, self.flag_dev, self.events = torch.zeros(T + 1, dtype=torch.int32), 0, None
+        else:
+            self.flags, self.flag_dev, self.events = _live_flags(sim, T)
+        self.live = None if self.flag_dev else torch.zeros(T + 1, dtype=torch.int32, device=dev)
+        self.args = N.craft_lang_step_args_t()
+        self.args.done = self.done.data_ptr()
+        self.args.success = self.success.data_ptr()
+        self.args.obs = self.obs.data_ptr()
+        if teach:
+            self.args.label_out = self.new_labels.data_ptr()
+
+    def tick(self, actions, alt=None, use_alt=None):
+        """One craft_step_lang launch, then the read of its any-live flag: True while some env
+        is still running."""
+        t, a, sim = self.ticks, self.args, self.sim
+        a.actions = actions.data_ptr()
+        a.alt_actions = None if alt is None else alt.data_ptr()
+        a.use_alt = None if use_alt is None else use_alt.data_ptr()
+        a.tick = t
+        a.action_record = self.seqs[t].data_ptr()
+        a.ask_record = self.asks[t].data_ptr()
+        a.transition_code = self.codes[t].data_ptr()
+        a.any_live = self.flag_dev + 4 * t if self.flag_dev else self.live[t].data_ptr()
+        sim._check(sim._L.craft_step_lang(sim._h, a, sim._stream()), "craft_step_lang")
+        self.ticks = t + 1
+        if sim._cpu:
+            return int(self.live[t]) != 0
+        if not self.flag_dev:
+            self.flags[t:t + 1].copy_(self.live[t:t + 1], non_blocking=True)
+        self.events[t].record()
+        self.events[t].synchronize()
+        return int(self.flags[t]) != 0
+
+
+def do_language_rollout(sim, spec, student, teacher, is_eval, mode, ref_actions=None):
+    """One rollout of sim.n_envs episodes under the protocol of the reference's language
+    trainer `mode` ("primitive", "interactive" or "active"); returns a LanguageRolloutInfo.
+
+    spec: (scenario, x, y, dir, task), each n_envs ints.  ref_actions (primitive only): each
+    env's demonstration, which teacher.instruct turns into its instruction
+    (primitive_language.py:26).  Eager loop: no graph capture, no lookahead."""
+    if mode not in MODES:
+        raise ValueError(f"mode {mode!r}: one of {MODES}")
+    if sim.config.max_timesteps <= 0:
+        raise ValueError("max_timesteps must be positive")
+    n, dev = sim.n_envs, sim.device
+    spec = [sim._i32(a, n) for a in spec]
+    task = spec[4].contiguous()
+    is_eval = bool(is_eval)
+    if mode == "primitive":
+        return _primitive(sim, spec, task, student, teacher, is_eval, ref_actions)
+    train = not is_eval
+    active = mode == "active"
+    student.init(n)
+    student.set_tasks(task, is_eval)
+    p = _Pass(sim, spec, teach=train)
+    # the teacher's label of every env's current state; a done env keeps its last one
+    labels = None
+    raised = torch.zeros((), dtype=torch.bool, device=dev)   # the reference's teacher raised
+    if train:
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        sim.teacher(action_out=labels)
+    instr = torch.full((n,), -1, dtype=torch.int32, device=dev)            # '<PAD>'
+    descriptions = [[PAD] for _ in range(n)] if active else [None] * n
+    num_interactions = 0
+    t = 0
+    while True:
+        obs = p.obs
+        alt = ask = None
+        if is_eval:
+            actions = _actions(student.act(obs, t), n, dev)
+        elif active:
+            actions, ask = student.act(obs, t)
+            actions = _actions(actions, n, dev)
+            ask = (torch.as_tensor(ask, device=dev).reshape(n) == ASK).to(torch.uint8).contiguous()
+            asked = ask != 0
+            # the teacher is asked about ASK envs only, done ones included (:51-54)
+            raised |= ((labels == -2) & asked).any()
+            instr = torch.where(asked, labels, instr)
+            student.set_instructions(instr)
+            alt = _actions(student.instructed_act(obs, t, ask), n, dev)
+        else:
+            raised |= (labels == -2).any()           # asked about every env, done or not (:49-51)
+            instr = labels
+            student.set_instructions(instr)
+            actions = _actions(student.instructed_act(obs, t), n, dev)
+        more = p.tick(actions, alt, ask)
+        if train:
+            # a slot done before the tick was not labelled (-1): it keeps its last label
+            labels = torch.where(p.new_labels == -1, labels, p.new_labels)
+        if train or not active:
+            # describe every env that stepped (active: that stepped on an instruction), in env
+            # order; the others keep their last description (:66-69, active :73-80)
+            rec = p.seqs[t].cpu().numpy()
+            codes = p.codes[t].cpu().numpy()
+            if active:
+                arec = p.asks[t].cpu().numpy()
+                codes = np.where(arec == 1, codes, -1)
+                num_interactions += int((arec == 1).sum())
+            else:
+                num_interactions += int((codes >= 0).sum()) if train else 0
+            for i, w in enumerate(teacher.describe_batch(rec, codes)):
+                if w is not None:
+                    descriptions[i] = [w]
+            if active:
+                student.receive(descriptions, ask)
+            else:
+                student.receive(descriptions)
+        student.terminate(p.done)
+        t += 1
+        if not more:
+            break
+    if train:
+        if active:
+            student.set_tasks(task, is_eval)
+        student.imitate_instructed()
+    num_steps = int((p.seqs[:t] >= 0).sum()) if train else 0
+    return _summary(sim, task, p, num_interactions, num_steps, raised)
+
+
+def _primitive(sim, spec, task, student, teacher, is_eval, ref_actions):
+    n, dev = sim.n_envs, sim.device
+    if ref_actions is None or len(ref_actions) != n:
+        raise ValueError("primitive mode needs ref_actions, one action sequence per env")
+    instructions = [teacher.instruct(None, ra) for ra in ref_actions]
+    L = max(1, max(len(w) for w in instructions))
+    instr = np.full((n, L), -1, dtype=np.int32)
+    for i, ws in enumerate(instructions):
+        instr[i, :len(ws)] = [WORDS.index(w) for w in ws]
+    instr = torch.as_tensor(instr, device=dev)
+    student.init(n)
+    student.set_tasks(task, is_eval)
+    student.set_instructions(instr)
+    num_interactions = 0 if is_eval else sum(len(w) for w in instructions)
+    raised = torch.zeros((), dtype=torch.bool, device=dev)
+
+    def run(instructed):
+        p = _Pass(sim, spec, teach=False)
+        while True:
+            t = p.ticks
+            act = student.instructed_act if instructed else student.act
+            more = p.tick(_actions(act(p.obs, t), n, dev))
+            student.terminate(p.done)
+            if not more:
+                return p
+
+    p = run(not is_eval)
+    num_steps = 0
+    if not is_eval:
+        num_steps = int((p.seqs[:p.ticks] >= 0).sum())
+        # whole-sequence describe per env, in env order (:69-75)
+        A = p.seqs[:p.ticks].t().cpu().numpy()
+        C = p.codes[:p.ticks].t().cpu().numpy()
+        descriptions = []
+        for i in range(n):
+            k = int((A[i] >= 0).sum())
+            descriptions.append(teacher.describe_codes(A[i, :k], C[i, :k]))
+        student.receive(descriptions)
+        # the second decoding, without exploration, from the same initial states (:77-119)
+        student.set_instructions(instr)
+        student.reset_history()
+        p = run(True)
+        student.imitate_instructed()
+    return _summary(sim, task, p, num_interactions, num_steps, raised)
+
+
+def _summary(sim, task, p, num_interactions, num_steps, raised):
+    """success / distances of the final states (primitive_language.py:121-133) with one
+    read-back: craft_rollout_distances, the flags and the latched-error word."""
+    n, dev, t = sim.n_envs, sim.device, p.ticks
+    buf = torch.zeros(4, dtype=torch.int32, device=dev)   # [0:2] the two flags, [2] raised
+    err = torch.zeros(4, dtype=torch.int32, device=dev)
+    distances = torch.empty(n, dtype=torch.int32, device=dev)
+    is_get = torch.empty(n, dtype=torch.uint8, device=dev)
+    n_actions = torch.empty(n, dtype=torch.int32, device=dev)
+    sim._check(sim._L.craft_rollout_distances(
+        sim._h, task.data_ptr(), p.success.data_ptr(), p.seqs.data_ptr(), p.seqs.shape[0],
+        distances.data_ptr(), is_get.data_ptr(), n_actions.data_ptr(), buf[0:2].data_ptr(),
+        sim._stream()), "craft_rollout_distances")
+    buf[2] = raised.to(torch.int32)
+    sim.error_word(out=err)
+    host = torch.cat([buf, err]).cpu().tolist()
+    if host[4]:
+        sim.check()                                  # raises: an error latched in the loop
+    if host[2]:
+        raise RolloutError("the teacher raised on the final state of an env that ended while "
+                           "others were still running")
+    if host[1]:
+        raise RolloutError("find_closest_resources found no target: len(None) "
+                           "(primitive_language.py:129-131)")
+    return LanguageRolloutInfo(action_seqs=p.seqs[:t], n_actions=n_actions, success=p.success,
+                               distances=distances, is_get=is_get.view(torch.bool),
+                               num_interactions=num_interactions, num_steps=num_steps, ticks=t)

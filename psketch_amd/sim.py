@@ -333,6 +333,51 @@ class CraftSim:
                         "craft_step")
         return obs
 
+    def step_lang(self, actions=None, seed=0, tick=0, alt_actions=None, use_alt=None, obs=None,
+                  done=None, success=None, action_record=None, ask_record=None,
+                  transition_code=None, any_live=None, labels=None, flags=0):
+        """One tick of the language trainers' rollout for every slot (include/craft.h
+        craft_step_lang): every running slot steps first (STOP too), then its timer drops and
+        done latches; success is satisfies() of the new state.  actions: int32 [N] or None for
+        the hashed draw; use_alt (uint8 [N]) picks alt_actions (int32 [N]) per slot, the active
+        trainer's ASK bit.  Outputs, each optional: done uint8, success int8 (-1 running or
+        None), action_record int32 and ask_record int8 (-1 for a slot done before the tick),
+        transition_code int8, any_live int32 [1], labels int32 [N]: the DemonstrationTeacher on
+        every new state in the same launch (-1 for a slot done before the tick)."""
+        n = self.n_envs
+        args = N.craft_lang_step_args_t()
+        keep = []
+
+        def put(field, t):
+            if t is not None:
+                keep.append(t)
+                setattr(args, field, t.data_ptr())
+
+        put("actions", self._i32(actions, n) if actions is not None else None)
+        put("alt_actions", self._i32(alt_actions, n) if alt_actions is not None else None)
+        if use_alt is not None:
+            ua = torch.as_tensor(use_alt, device=self.device)
+            ua = (ua != 0).to(torch.uint8).contiguous() if ua.dtype != torch.uint8 else ua.contiguous()
+            if ua.numel() != n:
+                raise ValueError(f"use_alt: expected {n} entries")
+            put("use_alt", ua)
+        for name, t, dt, shape in (("done", done, torch.uint8, (n,)),
+                                   ("success", success, torch.int8, (n,)),
+                                   ("action_record", action_record, torch.int32, (n,)),
+                                   ("ask_record", ask_record, torch.int8, (n,)),
+                                   ("transition_code", transition_code, torch.int8, (n,)),
+                                   ("any_live", any_live, torch.int32, (1,)),
+                                   ("label_out", labels, torch.int32, (n,))):
+            put(name, self._buf(name, t, dt, shape))
+        self._obs(obs)
+        put("obs", obs)
+        args.action_seed = seed & (2**64 - 1)
+        args.tick = int(tick)
+        args.flags = int(flags)
+        self._check(self._L.craft_step_lang(self._h, ctypes.byref(args), self._stream()),
+                    "craft_step_lang")
+        return obs
+
     def rollout(self, n_ticks, seed=0, tick0=0, actions=None, autoreset=True, obs=None,
                 reward=None, done=None, success=None):
         """n_ticks craft_step ticks in one launch (include/craft.h craft_rollout),
