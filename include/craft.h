@@ -385,6 +385,73 @@ typedef struct {
 } craft_lang_step_args_t;
 int craft_step_lang(craft_sim_t* sim, const craft_lang_step_args_t* args, void* stream);
 
+/* ---- the episode queue ---------------------------------------------------------
+ * CRAFT_STEP_AUTORESET puts a finished slot back on its own spec.  The episode queue gives it
+ * something new instead: a device-resident list of episode specs, a static assignment of its
+ * entries to slots, and a tick (craft_step_stream) that moves a finished slot onto its next
+ * entry.  One pass over a split (ImitationTrainer.evaluate, trainers/imitation.py:183-226) or an
+ * endless stream of fresh episodes for a student in the loop (CRAFT_QUEUE_WRAP) both sit on it. */
+
+/* Installs the queue: `specs` is device int32[count][5] = {scenario, x0, y0, dir0, task} (a host
+ * pointer on the CPU variant), the fields and ranges craft_reset checks, 1 <= count < 2^31.  A
+ * kernel checks every entry and packs it into a buffer the handle owns (8 bytes per entry:
+ * scenario | task << 24, then x | y << 8 | dir << 16), so a tick never meets an invalid entry and
+ * nothing is allocated on the step path.  Synchronous, like craft_pool_load.  An invalid entry
+ * fails the call with CRAFT_EINVAL (the message names the first such index) and the queue
+ * installed before, if any, stays in force.  Scenario indices are checked against the pool rows
+ * loaded at this call; a later craft_pool_load does not invalidate the queue (its entries then
+ * name whatever those rows hold).  Installing a queue does not move any slot, but the cursors of
+ * a craft_episode_begin made on the previous queue mean nothing on this one: craft_step_stream
+ * refuses until craft_episode_begin has been called again. */
+int craft_episode_queue(craft_sim_t* sim, const int32_t* specs, int64_t count);
+
+#define CRAFT_QUEUE_WRAP 1u   /* queue indices are taken mod count: the stream never runs out */
+
+/* craft_reset of every slot from the queue, stream-ordered.  The slot with global id g =
+ * env_id_base + i starts on entry first + g; its later episodes are first + g + k * stride,
+ * k = 1, 2, ...  A caller sharding over ranks passes stride = the total envs of all ranks, and
+ * every rank then runs the episodes a single large handle would have given those slots (the
+ * invariant the hashed draw keeps).  With CRAFT_QUEUE_WRAP the indices are taken mod count;
+ * without it an index >= count means the slot has run out, and its finished episode then freezes
+ * it exactly as craft_step without auto-reset does.  The assignment is static on purpose: a
+ * shared counter would balance the slots better, but which slot got which episode (and so every
+ * output row) would then depend on timing.  CRAFT_EINVAL: no queue installed, stride < 1,
+ * first < 0, or (without WRAP) a slot whose first index is already >= count.  `obs` as in
+ * craft_reset.  A later craft_reset or craft_set_state changes a slot's state but leaves its
+ * cursor alone: the slot's next restart still takes the entry after the one it was given here. */
+int craft_episode_begin(craft_sim_t* sim, int64_t first, int64_t stride, uint32_t flags, void* obs,
+                        void* stream);
+
+/* craft_step_ex / craft_step_teach with CRAFT_STEP_AUTORESET, except that a slot whose episode
+ * ends restarts on its next queue entry instead of its own spec.  The protocol is the same: done
+ * on STOP or at the time limit, success = satisfies() of the pre-step state, no step on the
+ * ending tick; done / success / reward, the action record, the transition code and the
+ * statistics are craft_step_ex's.  On a restart the slot takes the entry's scenario, pose and
+ * task, timer = max_timesteps, an empty inventory and nothing cleared; the init pose and the
+ * spec craft_get_state reports become the entry's.  The tick's obs row and label are features()
+ * and the teacher's answer of that new initial state under the new task.  A slot that has run
+ * out freezes: its row is its final state and its label -1.
+ *   label_out    int32[n] or NULL (no teacher in the launch), as craft_step_teach's;
+ *   episode_end  int32[n]: the queue index of the episode that ended this tick, else -1;
+ *   end_pose     int32[n]: x | y << 8 | dir << 16 of that episode's final state, else -1;
+ *   episode_now  int32[n]: the queue index the slot runs after the tick, -1 for a frozen slot
+ * (each may be NULL).  *any_live is set when some slot is still running after the tick, a slot
+ * that just restarted included, so a pass over the queue has ended when it stays 0.
+ * CRAFT_EINVAL: step.flags != CRAFT_STEP_AUTORESET, no craft_episode_begin since the queue was
+ * installed, or (with
+ * label_out) a launch under stream capture while pool rows wait for their teacher-table entries
+ * (craft_sim_sync_table).  Always the one-tile kernel: of craft_sim_tune_teach's knobs, lanes and
+ * table apply.  craft_step*, craft_step_lang, craft_rollout and craft_rollout_teach behave as
+ * before (their auto-reset restarts a slot on the spec it has now, the queue entry it last took). */
+typedef struct {
+  craft_step_args_t step;
+  int32_t* label_out;
+  int32_t* episode_end;
+  int32_t* end_pose;
+  int32_t* episode_now;
+} craft_stream_step_args_t;
+int craft_step_stream(craft_sim_t* sim, const craft_stream_step_args_t* args, void* stream);
+
 /* n_ticks consecutive craft_step ticks (tick0, tick0+1, ...) in one launch, with
  * results identical to n_ticks craft_step calls: each workgroup keeps its envs
  * on chip between ticks, so the per-tick prologue overlaps other workgroups'

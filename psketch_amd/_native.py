@@ -34,6 +34,7 @@ KIND_INERT, KIND_GRABBABLE, KIND_WORKSHOP, KIND_WATER, KIND_STONE = range(5)
 GOAL_OTHER, GOAL_GET, GOAL_MAKE, GOAL_GO, GOAL_USE = range(5)
 
 STEP_AUTORESET = 1
+QUEUE_WRAP = 1
 
 KERNEL_TILE, KERNEL_TICK2 = 1, 2
 KERNEL_NAMES = {KERNEL_TILE: "tile_kernel", KERNEL_TICK2: "tick2_kernel"}
@@ -116,6 +117,16 @@ class craft_lang_step_args_t(ctypes.Structure):
     ]
 
 
+class craft_stream_step_args_t(ctypes.Structure):
+    _fields_ = [
+        ("step", craft_step_args_t),
+        ("label_out", ctypes.c_void_p),
+        ("episode_end", ctypes.c_void_p),
+        ("end_pose", ctypes.c_void_p),
+        ("episode_now", ctypes.c_void_p),
+    ]
+
+
 class craft_rollout_teach_args_t(ctypes.Structure):
     _fields_ = [
         ("actions", ctypes.c_void_p),
@@ -176,6 +187,9 @@ SIGNATURES = {
     "craft_step_ex": (_i32, [_vp, ctypes.POINTER(craft_step_args_t), _vp]),
     "craft_step_teach": (_i32, [_vp, ctypes.POINTER(craft_step_args_t), _vp, _vp]),
     "craft_step_lang": (_i32, [_vp, ctypes.POINTER(craft_lang_step_args_t), _vp]),
+    "craft_episode_queue": (_i32, [_vp, _vp, _i64]),
+    "craft_episode_begin": (_i32, [_vp, _i64, _i64, _u32, _vp, _vp]),
+    "craft_step_stream": (_i32, [_vp, ctypes.POINTER(craft_stream_step_args_t), _vp]),
     "craft_rollout": (_i32, [_vp, _vp, _u64, _i64, _i32, _u32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "craft_rollout_teach": (_i32, [_vp, ctypes.POINTER(craft_rollout_teach_args_t), _vp]),
     "craft_stats": (_i32, [_vp, _vp, _i32, _vp]),

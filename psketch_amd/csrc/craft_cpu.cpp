@@ -125,6 +125,12 @@ struct craft_sim {
   int tile = 64, obs_store = 2, resident_cap = 0, rollout_chunk = 0, rollout_threads = 0, teach_kernel = 0;
   int teach_lanes = 0, teach_table = 0;
   int threads = 1;
+  // the episode queue: the specs as given (checked at install), each slot's index (-1: run out)
+  struct QueueEntry { int32_t scen, x, y, dir, task; };
+  std::vector<QueueEntry> queue;
+  std::vector<int64_t> cursor;
+  int64_t q_stride = 0;
+  bool q_wrap = false, q_begun = false;
   std::string last_error;
 };
 
@@ -1039,6 +1045,178 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* /*str
   s->stats[1] += n_ended.load();
   s->stats[2] += n_steps.load();
   if (x->any_live && running.load()) *x->any_live = 1;
+  return CRAFT_OK;
+}
+
+// ---- the episode queue ------------------------------------------------------------------------
+// Written out on its own (no call into tick_slot): this library is the second implementation
+// the HIP kernels are checked against.
+
+int craft_episode_queue(craft_sim_t* s, const int32_t* specs, int64_t count) {
+  if (!s) return CRAFT_EINVAL;
+  if (!specs || count < 1 || count > (int64_t)INT32_MAX)
+    return fail(s, CRAFT_EINVAL, "craft_episode_queue: specs must hold 1 .. 2^31 - 1 entries");
+  std::vector<craft_sim::QueueEntry> q((size_t)count);
+  for (int64_t i = 0; i < count; ++i) {
+    const int32_t* e = specs + 5 * i;
+    const bool ok = e[0] >= 0 && e[0] < s->pool_count && e[1] >= 1 && e[1] <= s->W - 2 && e[2] >= 1 &&
+                    e[2] <= s->H - 2 && e[3] >= 0 && e[3] <= 3 && e[4] >= 0 && e[4] < s->cfg.n_tasks;
+    if (!ok)                                          // the queue installed before stays in force
+      return fail(s, CRAFT_EINVAL, "craft_episode_queue: entry " + std::to_string(i) +
+                                       " is invalid (scenario, position, direction or task out of range)");
+    q[(size_t)i] = {e[0], e[1], e[2], e[3], e[4]};
+  }
+  s->queue.swap(q);
+  s->q_begun = false;
+  return CRAFT_OK;
+}
+
+int craft_episode_begin(craft_sim_t* s, int64_t first, int64_t stride, uint32_t flags, void* obs, void* stream) {
+  if (!s) return CRAFT_EINVAL;
+  if (s->queue.empty()) return fail(s, CRAFT_EINVAL, "craft_episode_begin: no episode queue installed (craft_episode_queue)");
+  if (stride < 1) return fail(s, CRAFT_EINVAL, "craft_episode_begin: stride must be >= 1");
+  if (first < 0) return fail(s, CRAFT_EINVAL, "craft_episode_begin: first must be >= 0");
+  if (flags & ~CRAFT_QUEUE_WRAP) return fail(s, CRAFT_EINVAL, "craft_episode_begin: unknown flag");
+  if (obs && (reinterpret_cast<uintptr_t>(obs) & 15u))
+    return fail(s, CRAFT_EINVAL, "craft_episode_begin: obs must be 16-byte aligned");
+  const bool wrap = (flags & CRAFT_QUEUE_WRAP) != 0;
+  const int64_t count = (int64_t)s->queue.size(), n = s->n_envs;
+  if (first > INT64_MAX - s->env_base - n) return fail(s, CRAFT_EINVAL, "craft_episode_begin: first is out of range");
+  const int64_t g0 = first + s->env_base;
+  if (!wrap && n > 0 && g0 + n - 1 >= count)
+    return fail(s, CRAFT_EINVAL, "craft_episode_begin: slot " + std::to_string(std::max<int64_t>(count - g0, 0)) +
+                                     " would start past the end of the queue (" + std::to_string(count) + " entries)");
+  s->cursor.assign((size_t)n, -1);
+  std::vector<int32_t> r((size_t)(5 * n));
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t q = wrap ? (g0 + i) % count : g0 + i;
+    const craft_sim::QueueEntry& e = s->queue[(size_t)q];
+    s->cursor[(size_t)i] = q;
+    r[i] = e.scen; r[n + i] = e.x; r[2 * n + i] = e.y; r[3 * n + i] = e.dir; r[4 * n + i] = e.task;
+  }
+  const int rc = craft_reset(s, r.data(), r.data() + n, r.data() + 2 * n, r.data() + 3 * n, r.data() + 4 * n, obs, stream);
+  if (rc != CRAFT_OK) return rc;
+  s->q_stride = stride;
+  s->q_wrap = wrap;
+  s->q_begun = true;
+  return CRAFT_OK;
+}
+
+int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* /*stream*/) {
+  if (!s || !x) return CRAFT_EINVAL;
+  const craft_step_args_t& p = x->step;
+  if (p.flags != CRAFT_STEP_AUTORESET)
+    return fail(s, CRAFT_EINVAL, "craft_step_stream: step.flags must be CRAFT_STEP_AUTORESET");
+  if (s->queue.empty() || !s->q_begun)
+    return fail(s, CRAFT_EINVAL, "craft_step_stream: craft_episode_begin has not put the slots on the queue");
+  if (x->label_out && 4 * s->C > 1000)
+    return fail(s, CRAFT_EINVAL, "craft_step_stream: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  const int rc = step_check(s, &p);
+  if (rc) return rc;
+  const int64_t count = (int64_t)s->queue.size();
+  std::atomic<int64_t> n_succ{0}, n_ended{0}, n_steps{0};
+  std::atomic<bool> running{false};
+  parallel_for(s, s->n_envs, [&](int64_t lo, int64_t hi) {
+    int64_t succs = 0, ended = 0, steps = 0;
+    bool some_running = false;
+    std::vector<uint8_t> g(CRAFT_MAX_CELLS), row(s->F);
+    for (int64_t i = lo; i < hi; ++i) {
+      Agent a = unpack_state(s->state[i]);
+      const bool valid = a.x >= 1 && a.x <= s->W - 2 && a.y >= 1 && a.y <= s->H - 2 && a.scen < s->pool_count;
+      if (!valid) {                                    // never initialised by reset / set_state
+        latch(s, CRAFT_EINVAL, i);
+        if (p.transition_code) p.transition_code[i] = -1;
+        if (p.obs) {
+          std::memset(row.data(), 0, s->F);
+          put_obs(s->obs_fmt, p.obs, i, s->F, row.data());
+        }
+        if (x->label_out) x->label_out[i] = -2;
+        continue;
+      }
+      int action = p.actions ? p.actions[i]
+                             : (int)((uint32_t)(splitmix64(p.action_seed ^ ((uint64_t)(s->env_base + i) << 20) ^
+                                                           (uint64_t)p.tick) >> 32) % 6u);
+      if (p.behavior_clone && p.behavior_clone[i]) action = p.ref_actions[i];
+      uint8_t* iv = s->inv.data() + 32 * i;
+      uint32_t* m = s->mask.data() + 8 * i;
+      env_grid(s, i, a.scen, g.data());
+      const bool ran = a.frozen == 0;                  // the slot spends a timestep this tick
+      bool ends = false;
+      int sat = -1, code = -1;
+      int32_t ended_index = -1, ended_pose = -1;
+      if (ran) {
+        a.timer -= 1;
+        ends = action == CRAFT_STOP || a.timer <= 0;
+      }
+      if (ends || !ran) sat = satisfies(s, g.data(), iv, a, a.task);   // of the state as it is (no step)
+      if (ends) {
+        const int64_t cur = s->cursor[(size_t)i];
+        ended_index = (int32_t)cur;
+        ended_pose = (int32_t)((uint32_t)a.x | ((uint32_t)a.y << 8) | ((uint32_t)a.dir << 16));
+        int64_t next = -1;
+        if (cur >= 0) {
+          // (stride may be huge: the test against what is left cannot overflow)
+          if (s->q_wrap) next = (cur + s->q_stride % count) % count;
+          else if (s->q_stride < count - cur) next = cur + s->q_stride;
+        }
+        s->cursor[(size_t)i] = next;
+        if (next >= 0) {                               // the next episode: CraftScenario.init of its spec
+          const craft_sim::QueueEntry& e = s->queue[(size_t)next];
+          a.scen = e.scen; a.task = e.task; a.x = e.x; a.y = e.y; a.dir = e.dir;
+          a.timer = s->cfg.max_timesteps;
+          s->init[i] = (uint32_t)e.x | ((uint32_t)e.y << 8) | ((uint32_t)e.dir << 16);
+          std::memset(iv, 0, 32);
+          std::memset(m, 0, 32);
+          std::memcpy(g.data(), s->pool.data() + (size_t)a.scen * s->C, s->C);
+        } else {                                       // run out: frozen as craft_step leaves it
+          a.frozen = 1;
+          if (a.timer < 0) a.timer = 0;
+        }
+      } else if (ran) {
+        if (action < 0 || action >= CRAFT_N_ACTIONS) {
+          latch(s, CRAFT_EBADACTION, i);
+        } else {
+          const int ox = a.x, oy = a.y;
+          bool ic = false, mc = false;
+          transition(s, g.data(), iv, a, m, action, ic, mc, i);
+          code = transition_code(ox, oy, a, ic);
+        }
+      }
+      s->state[i] = pack_state(a);
+      const bool is_done = ends || !ran;
+      if (p.done) p.done[i] = is_done ? 1 : 0;
+      if (p.success) p.success[i] = (int8_t)sat;
+      if (p.reward) p.reward[i] = (ends && sat == 1) ? 1.0f : 0.0f;
+      if (p.action_record) p.action_record[i] = ran ? action : -1;
+      if (p.transition_code) p.transition_code[i] = (int8_t)code;
+      if (x->episode_end) x->episode_end[i] = ended_index;
+      if (x->end_pose) x->end_pose[i] = ended_pose;
+      if (x->episode_now) x->episode_now[i] = a.frozen ? -1 : (int32_t)s->cursor[(size_t)i];
+      steps += ran;
+      ended += ends;
+      succs += ends && sat == 1;
+      some_running = some_running || !a.frozen;
+      if (p.obs) {
+        features(s, g.data(), iv, a, row.data());
+        put_obs(s->obs_fmt, p.obs, i, s->F, row.data());
+      }
+      if (x->label_out) {
+        int label = -1;                                // a frozen slot: imitation.py:50-51
+        if (!a.frozen) {
+          int len = -1, err = 0;
+          label = teach(s, g.data(), iv, a, a.task, false, len, err);
+          if (err) latch(s, err, i);
+        }
+        x->label_out[i] = label;
+      }
+    }
+    n_succ += succs; n_ended += ended; n_steps += steps;
+    if (some_running) running = true;
+  });
+  s->stats[0] += n_succ.load();
+  s->stats[1] += n_ended.load();
+  s->stats[2] += n_steps.load();
+  if (p.any_live && running.load()) *p.any_live = 1;
   return CRAFT_OK;
 }
 

@@ -31,7 +31,8 @@ constexpr int kMinTileEnvs = 16;
 constexpr int kInvStride = 36;     // LDS bytes per inventory row (9 dwords: bank-spread)
 
 // MODE_LANG: the language trainers' tick (craft_step_lang): step first, then the timer
-enum Mode { MODE_TICK = 0, MODE_TRANSITION = 1, MODE_OBSERVE = 2, MODE_RESET = 3, MODE_LANG = 4 };
+// MODE_STREAM: MODE_TICK whose auto-reset takes the slot's next episode-queue entry (craft_step_stream)
+enum Mode { MODE_TICK = 0, MODE_TRANSITION = 1, MODE_OBSERVE = 2, MODE_RESET = 3, MODE_LANG = 4, MODE_STREAM = 5 };
 
 struct SimView {
   const uint8_t* pool;
@@ -220,6 +221,18 @@ struct TileArgs {
   int8_t* code;            // transition codes (craft_step_ex, craft_transition)
   int32_t* label;          // craft_step_teach: teacher label of every env's new state
   int8_t* ask;             // MODE_LANG: the use_alt bit of a slot that stepped, else -1
+  // MODE_STREAM (craft_step_stream), appended so that the other modes' argument words stay put:
+  // the packed queue (.x = scenario | task << 24, .y = x | y << 8 | dir << 16), each slot's
+  // cursor (the queue index of its current episode, -1 once it has run out), the entries and
+  // the index step to a slot's next episode (both < 2^31; craft_episode_begin reduces them),
+  // wrap = CRAFT_QUEUE_WRAP, and the tick's three extra outputs (each may be null)
+  const uint2* q_entries;
+  int32_t* q_cursor;
+  uint32_t q_count, q_step;
+  uint32_t q_wrap;
+  int32_t* ep_end;
+  int32_t* end_pose;
+  int32_t* ep_now;
 };
 
 struct RolloutArgs {       // craft_rollout: n_ticks ticks in one launch

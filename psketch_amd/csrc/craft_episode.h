@@ -1,7 +1,7 @@
 // craft_episode.h — the one definition of what every tick kernel must agree on: the per-env
 // body of ImitationTrainer.do_rollout (trainers/imitation.py:59-73) in pieces, the language
-// trainers' variant of it (tile_kernel's MODE_LANG), and the K-tick kernels' cleared-cell
-// bookkeeping.
+// trainers' variant of it (tile_kernel's MODE_LANG), the episode queue's restart (MODE_STREAM),
+// and the K-tick kernels' cleared-cell bookkeeping.
 //
 // Everything here is __device__ __forceinline__, works on state passed by reference, touches
 // no LDS of its own and has no barrier, so a kernel keeps its own scheduling (wave roles,
@@ -75,6 +75,61 @@ __device__ __forceinline__ void language_step_end(Agent& s, const int& act, int&
 __device__ __forceinline__ void restart_agent(Agent& s, uint32_t init_word, int maxT) {
   s.x = init_word & 0xff; s.y = (init_word >> 8) & 0xff; s.dir = (init_word >> 16) & 3;
   s.timer = maxT;
+}
+
+// ---- the episode queue (craft_step_stream: tile_kernel's MODE_STREAM) -------------------------
+// A slot's cursor is the queue index of the episode it runs, -1 once it has run out.  Its next
+// episode is `step` entries on: under wrap step = stride mod count and the index wraps, else
+// step = min(stride, count) and an index past the end means there is none (-1).  count < 2^31
+// and cur < count (craft_episode_queue / craft_episode_begin see to it), so the sum fits 32 bits.
+__device__ __forceinline__ int32_t queue_next(int32_t cur, const uint32_t& count, const uint32_t& step, const uint32_t& wrap) {
+  if (cur < 0) return -1;
+  uint32_t nx = (uint32_t)cur + step;
+  if (nx >= count) {
+    if (!wrap) return -1;
+    nx -= count;
+  }
+  return (int32_t)nx;
+}
+
+// Whether protocol_step will end the slot's episode this tick: known from the state word and the
+// action alone, so the next queue entry can be fetched beside the scenario row.
+__device__ __forceinline__ bool episode_ends(const Agent& s, int act) {
+  return !s.frozen && (act == CRAFT_STOP || s.timer <= 1);
+}
+
+// A packed queue entry (.x = scenario | task << 24, .y = the init word) as the agent's new
+// episode; the caller empties the inventory and the mask and reloads the grid row.
+__device__ __forceinline__ void restart_from_entry(Agent& s, const uint2& e, int maxT) {
+  s.scen = (int)(e.x & 0xffffffu);
+  s.task = (int)(e.x >> 24);
+  restart_agent(s, e.y, maxT);
+}
+
+// x | y << 8 | dir << 16: an init word, and craft_step_stream's end_pose.
+__device__ __forceinline__ uint32_t pose_word(const Agent& s) {
+  return (uint32_t)s.x | ((uint32_t)s.y << 8) | ((uint32_t)s.dir << 16);
+}
+
+// pool[scenario] (L2-resident) into the env's LDS grid row, in the lanes that restart onto another
+// scenario only: every 16-byte chunk of a batch of QB is requested before the first is used, so
+// the restart costs one more L2 round trip per batch (QB 16: the whole row at once).
+template <int QB>
+__device__ __forceinline__ void reload_grid_row(const uint4* pool_row, uint32_t* grid, const int& CS) {
+  const int nchunk = CS >> 4;
+#pragma unroll
+  for (int b = 0; b < CRAFT_MAX_CELLS / 16; b += QB) {
+    uint4 c[QB];
+#pragma unroll
+    for (int q = 0; q < QB; ++q)
+      if (b + q < nchunk) c[q] = pool_row[b + q];
+#pragma unroll
+    for (int q = 0; q < QB; ++q)
+      if (b + q < nchunk) {
+        grid[4 * (b + q) + 0] = c[q].x; grid[4 * (b + q) + 1] = c[q].y;
+        grid[4 * (b + q) + 2] = c[q].z; grid[4 * (b + q) + 3] = c[q].w;
+      }
+  }
 }
 
 // An episode that ends without auto-reset stays as it is until the next reset.

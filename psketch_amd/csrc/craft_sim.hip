@@ -1,7 +1,8 @@
 // craft_sim.hip — host side of the C ABI (include/craft.h): handle lifetime,
 // scenario pool, launches, state I/O and episode statistics.
 // Kernels: craft_tile.hip (tick / transition / observe / reset), craft_tick_lang.hip (the
-// language trainers' tick), craft_rollout.hip (multi-tick), craft_teacher.hip,
+// language trainers' tick), craft_tick_stream.hip (the episode queue and its tick),
+// craft_rollout.hip (multi-tick), craft_teacher.hip,
 // craft_scenarios.hip (pool generation).
 #include <algorithm>
 #include <cstdlib>
@@ -30,6 +31,12 @@ hipError_t launch_tick_teach(int tl, int nw, int win, int tile, const SimView& v
 hipError_t launch_tick2(int tl, int nw, const SimView& v, const TileArgs& a, size_t lds, hipStream_t st);
 hipError_t launch_tick_lang(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
                             hipStream_t st);
+hipError_t launch_tick_stream(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
+                              hipStream_t st);
+hipError_t launch_queue_pack(const SimView& v, const int32_t* specs, int64_t count, uint2* out,
+                             unsigned long long* first_bad, hipStream_t st);
+hipError_t launch_queue_begin(const uint2* entries, int64_t count, int64_t first_gid, int wrap, int64_t n,
+                              int32_t* cursor, int32_t* r, hipStream_t st);
 size_t tick2_lds_bytes(int tl, int nw, int GS, int F);
 hipError_t launch_teach_table(int nw, const SimView& v, int32_t first, int32_t count, const int32_t* kinds,
                               hipStream_t st);
@@ -186,6 +193,14 @@ struct craft_sim {
   uint64_t queue1_next = 0;         // queue[1] (the split kernel's per-unit path) at the next launch
   uint64_t queue_next = 0;          // the counter's value at the next launch (every launch adds
                                     // its units + its grid: one fetch past the end per workgroup)
+  // the episode queue (craft_episode_queue / craft_episode_begin / craft_step_stream)
+  uint2* d_queue = nullptr;         // packed entries
+  int64_t q_count = 0;
+  int32_t* d_cursor = nullptr;      // [n_envs] each slot's queue index (-1: run out)
+  int32_t* d_qreset = nullptr;      // [5][n_envs] craft_episode_begin's inputs to the reset kernel
+  unsigned long long* d_qbad = nullptr;   // the lowest invalid index of a queue being installed
+  uint32_t q_step = 0, q_wrap = 0;  // craft_episode_begin's stride (reduced, craft_episode.h) and WRAP
+  bool q_begun = false;             // craft_episode_begin since the queue was installed
   std::string last_error;
 };
 
@@ -688,6 +703,10 @@ int craft_sim_destroy(craft_sim_t* s) {
   (void)hipFree(s->d_ttab);
   (void)hipFree(s->d_ttab4);
   (void)hipFree(s->d_ttcells);
+  (void)hipFree(s->d_queue);
+  (void)hipFree(s->d_cursor);
+  (void)hipFree(s->d_qreset);
+  (void)hipFree(s->d_qbad);
   delete s;
   return CRAFT_OK;
 }
@@ -954,6 +973,125 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* strea
                                 v, a, lds, st);
   }
   if (e != hipSuccess) return hip_fail(s, e, "craft_step_lang launch");
+  return CRAFT_OK;
+}
+
+int craft_episode_queue(craft_sim_t* s, const int32_t* specs, int64_t count) {
+  if (!s) return CRAFT_EINVAL;
+  if (!specs || count < 1 || count > (int64_t)INT32_MAX)
+    return fail(s, CRAFT_EINVAL, "craft_episode_queue: specs must hold 1 .. 2^31 - 1 entries");
+  HIP_TRY(s, hipSetDevice(s->device));
+  // the handle's own buffers, once: the cursors, craft_episode_begin's reset inputs, the check's word
+  if (!s->d_cursor) {
+    int32_t* cur = nullptr;
+    int32_t* rs = nullptr;
+    unsigned long long* bad = nullptr;
+    const size_t nb = (size_t)std::max<int64_t>(s->n_envs, 1) * sizeof(int32_t);
+    if (hipMalloc(&cur, nb) != hipSuccess || hipMalloc(&rs, 5 * nb) != hipSuccess ||
+        hipMalloc(&bad, sizeof(unsigned long long)) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(cur);
+      (void)hipFree(rs);
+      (void)hipFree(bad);
+      return fail(s, CRAFT_ENOMEM, "craft_episode_queue: out of device memory");
+    }
+    s->d_cursor = cur;
+    s->d_qreset = rs;
+    s->d_qbad = bad;
+  }
+  uint2* q = nullptr;
+  if (hipMalloc(&q, (size_t)count * sizeof(uint2)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(s, CRAFT_ENOMEM, "craft_episode_queue: out of device memory");
+  }
+  unsigned long long bad = ~0ull;
+  hipError_t e = hipMemcpy(s->d_qbad, &bad, sizeof(bad), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = craft::launch_queue_pack(s->view, specs, count, q, s->d_qbad, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(&bad, s->d_qbad, sizeof(bad), hipMemcpyDeviceToHost);   // (waits for the kernel)
+  if (e != hipSuccess) {
+    (void)hipFree(q);
+    return hip_fail(s, e, "craft_episode_queue");
+  }
+  if (bad != ~0ull) {
+    (void)hipFree(q);                        // the queue installed before stays in force
+    return fail(s, CRAFT_EINVAL, "craft_episode_queue: entry " + std::to_string(bad) +
+                                     " is invalid (scenario, position, direction or task out of range)");
+  }
+  // ticks of the old queue may still be running on some stream: they finish first
+  HIP_TRY(s, hipDeviceSynchronize());
+  (void)hipFree(s->d_queue);
+  s->d_queue = q;
+  s->q_count = count;
+  s->q_begun = false;                        // cursors of the old queue mean nothing on this one
+  return CRAFT_OK;
+}
+
+int craft_episode_begin(craft_sim_t* s, int64_t first, int64_t stride, uint32_t flags, void* obs, void* stream) {
+  if (!s) return CRAFT_EINVAL;
+  if (!s->d_queue) return fail(s, CRAFT_EINVAL, "craft_episode_begin: no episode queue installed (craft_episode_queue)");
+  if (stride < 1) return fail(s, CRAFT_EINVAL, "craft_episode_begin: stride must be >= 1");
+  if (first < 0) return fail(s, CRAFT_EINVAL, "craft_episode_begin: first must be >= 0");
+  if (flags & ~CRAFT_QUEUE_WRAP) return fail(s, CRAFT_EINVAL, "craft_episode_begin: unknown flag");
+  if (obs && !aligned16(obs)) return fail(s, CRAFT_EINVAL, "craft_episode_begin: obs must be 16-byte aligned");
+  const bool wrap = (flags & CRAFT_QUEUE_WRAP) != 0;
+  const int64_t count = s->q_count;
+  if (first > INT64_MAX - s->env_base - s->n_envs)
+    return fail(s, CRAFT_EINVAL, "craft_episode_begin: first is out of range");
+  const int64_t g0 = first + s->env_base;
+  if (!wrap && s->n_envs > 0 && g0 + s->n_envs - 1 >= count)
+    return fail(s, CRAFT_EINVAL, "craft_episode_begin: slot " + std::to_string(std::max<int64_t>(count - g0, 0)) +
+                                     " would start past the end of the queue (" + std::to_string(count) + " entries)");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const hipError_t e = craft::launch_queue_begin(s->d_queue, count, g0, wrap ? 1 : 0, s->n_envs, s->d_cursor,
+                                                 s->d_qreset, st);
+  if (e != hipSuccess) return hip_fail(s, e, "craft_episode_begin launch");
+  const int64_t n = s->n_envs;
+  const int rc = craft_reset(s, s->d_qreset, s->d_qreset + n, s->d_qreset + 2 * n, s->d_qreset + 3 * n,
+                             s->d_qreset + 4 * n, obs, stream);
+  if (rc != CRAFT_OK) return rc;
+  s->q_step = (uint32_t)(wrap ? stride % count : std::min(stride, count));
+  s->q_wrap = wrap ? 1u : 0u;
+  s->q_begun = true;
+  return CRAFT_OK;
+}
+
+int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (x->step.flags != CRAFT_STEP_AUTORESET)
+    return fail(s, CRAFT_EINVAL, "craft_step_stream: step.flags must be CRAFT_STEP_AUTORESET");
+  if (!s->d_queue || !s->q_begun)
+    return fail(s, CRAFT_EINVAL, "craft_step_stream: craft_episode_begin has not put the slots on the queue");
+  if (x->label_out && 4 * s->view.C > 1000)
+    return fail(s, CRAFT_EINVAL, "craft_step_stream: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  TileArgs a;
+  const int rc = step_args(s, &x->step, a);
+  if (rc != CRAFT_OK) return rc;
+  a.label = x->label_out;
+  a.q_entries = s->d_queue;
+  a.q_cursor = s->d_cursor;
+  a.q_count = (uint32_t)s->q_count;
+  a.q_step = s->q_step;
+  a.q_wrap = s->q_wrap;
+  a.ep_end = x->episode_end;
+  a.end_pose = x->end_pose;
+  a.ep_now = x->episode_now;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipError_t e;
+  if (!x->label_out) {
+    e = craft::launch_tick_stream(0, 0, s->cfg.window_width, s->tile, s->view, a, tile_lds_bytes(s, s->tile), st);
+  } else {
+    const int frc = flush_table(s, stream, "craft_step_stream");
+    if (frc != CRAFT_OK) return frc;
+    SimView v = teach_view(s);
+    v.tt_fused = s->teach_table != 2;
+    // the one-tile kernel in craft_step_teach's shape: its tile, its lanes, its LDS
+    const int tile = teach_tile(s);
+    const size_t lds = (size_t)craft::lds_layout(tile, s->view.GS, s->view.F).bytes +
+                       (((size_t)s->view.n_tasks * CRAFT_MAX_SUBTASKS + 15) & ~size_t(15));
+    e = craft::launch_tick_stream(one_tile_lanes(s), craft::teach_words(s->view.W, s->view.H), s->cfg.window_width,
+                                  tile, v, a, lds, st);
+  }
+  if (e != hipSuccess) return hip_fail(s, e, "craft_step_stream launch");
   return CRAFT_OK;
 }
 

@@ -25,6 +25,9 @@ namespace craft {
 
 // MODE_LANG (craft_step_lang) is the tick of the language trainers' protocol: the same phases,
 // with the step before the timer and satisfies() read off the new state (craft_episode.h).
+// MODE_STREAM (craft_step_stream) is MODE_TICK under auto-reset whose restart takes the slot's next
+// episode-queue entry: the lanes that restart (and only they) fetch the entry, reload their grid
+// row from the new scenario's pool row and, with a teacher, the scenario's teacher words.
 //
 // TL > 0 (MODE_TICK and MODE_LANG only): TILE * TL more threads run the DemonstrationTeacher on
 // every env's new state (craft_step_teach), TL lanes per env, while the first
@@ -77,7 +80,12 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
   const int nE = (int)min((int64_t)TILE, a.n - env0);
   const bool want_obs = a.obs != nullptr;
   const int F = v.F;
-  constexpr bool kTick = MODE == MODE_TICK || MODE == MODE_LANG;   // a rollout tick of either protocol
+  constexpr bool kEp = MODE == MODE_TICK || MODE == MODE_STREAM;   // the imitation trainer's tick
+  // MODE_STREAM: 16-byte chunks in flight of a restart's new grid row.  16 = any row in one round
+  // trip; beside teacher waves 10 (a 12x12 row's 9 chunks still at once): 16 took the 3x3 default
+  // shape from 76 to 89 VGPRs, five waves per SIMD where the tick has six
+  constexpr int kReloadBatch = TL > 0 ? 10 : 16;
+  constexpr bool kTick = kEp || MODE == MODE_LANG;                 // a rollout tick of either protocol
 
   STAMP(0);
   // ---- A + C: wave 0, one lane per env ------------------------------------------------------
@@ -87,12 +95,14 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
     uint32_t init_word = 0;
     int act = 0, ref = 0;
     uint32_t bc = 0;
+    int32_t cur = -1, nxt = -1;                            // MODE_STREAM: the slot's queue cursor, its next
+    uint2 qe = make_uint2(0u, 0u);                         // and that entry
     uint64_t st = 0;
     uint4 i0 = make_uint4(0, 0, 0, 0), i1 = i0, m0 = i0, m1 = i0;
     Agent s{};
     if (live) {
       const int64_t i = env0 + tid;
-      slot = (MODE == MODE_TICK || MODE == MODE_RESET || !a.src) ? i : (int64_t)a.src[i];
+      slot = (kEp || MODE == MODE_RESET || !a.src) ? i : (int64_t)a.src[i];
       dslot = (MODE == MODE_TRANSITION && a.dst) ? (int64_t)a.dst[i] : slot;
       if (slot < 0 || slot >= v.n_envs || dslot < 0 || dslot >= v.n_envs) {
         latch_error(v.err, CRAFT_ERANGE, i);
@@ -102,6 +112,17 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
     // Every independent load of the env first, no result used before the last is issued (a
     // wave waits for its loads in issue order): state, inventory, mask, restart spec, action and
     // clone flag + label, then the static tables into registers; one round trip, then the row.
+    // (MODE_STREAM: the cursor and the action first.  With the state word they say whether the
+    // episode ends, and the fetch of the next queue entry and the row loads behind it then wait
+    // for these and the state, not for the inventory and the mask queued after them)
+    if (MODE == MODE_STREAM && live) {
+      cur = a.q_cursor[slot];
+      if (a.actions) act = a.actions[slot];
+      if (a.bc) {
+        bc = a.bc[slot];
+        ref = a.ref[slot];
+      }
+    }
     if (live && MODE != MODE_RESET) {
       st = v.state[slot];
       i0 = v.inv[2 * slot];
@@ -109,7 +130,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       m0 = v.mask[2 * slot];
       m1 = v.mask[2 * slot + 1];
       if (MODE == MODE_TICK || MODE == MODE_TRANSITION) init_word = v.init[slot];
-      if (kTick) {
+      if (MODE == MODE_TICK || MODE == MODE_LANG) {
         if (a.actions) act = a.actions[slot];
         // (MODE_LANG: use_alt and alt_actions, the same two loads in the same batch)
         if (a.bc) {
@@ -171,6 +192,12 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
         }
       }
     }
+    // MODE_STREAM: a slot whose episode ends this tick (the state word and the action say so)
+    // fetches its next queue entry now, beside the scenario row, not after it
+    if (MODE == MODE_STREAM && live && episode_ends(s, act)) {
+      nxt = queue_next(cur, a.q_count, a.q_step, a.q_wrap);
+      if (nxt >= 0) qe = a.q_entries[nxt];
+    }
     uint8_t* g = s_grid + tid * v.GS;
     uint32_t conn = 0, tcw0 = ~0u, tcw1 = ~0u;           // TL > 0: the scenario's free cells connected,
     if (TL > 0 && live) {                                  // its clearable cells the teacher table lists
@@ -224,18 +251,49 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       // The LDS row holds pool[scenario]; cells cleared this episode are applied
       // lazily, so an auto-reset (which restores exactly that row) needs no reload.
       bool restart = false;
-      if (MODE == MODE_TICK) {
+      if (kEp) {
         // per-env body of ImitationTrainer.do_rollout, trainers/imitation.py:59-73
         protocol_step(s, act, a.flags, d, counted, restart);
         // satisfies() of the pre-step state: only the facing cell and the inventory matter
         if (d) succ = satisfies_masked(v, g, iv, m, s, s_task[s.task]);
       }
+      if (MODE == MODE_STREAM) {
+        if (restart && nxt < 0) restart = false;          // the slot has run out: it freezes below
+        if (counted && d) {
+          const int64_t i = env0 + tid;
+          if (a.ep_end) a.ep_end[i] = cur;
+          if (a.end_pose) a.end_pose[i] = (int32_t)pose_word(s);
+          a.q_cursor[slot] = nxt;
+          cur = nxt;
+        } else {
+          const int64_t i = env0 + tid;
+          if (a.ep_end) a.ep_end[i] = -1;
+          if (a.end_pose) a.end_pose[i] = -1;
+        }
+      }
       if (!restart) apply_mask_to_row(m, g);              // cells cleared this episode
       if (MODE == MODE_RESET) {
         inv_changed = mask_changed = true;
-      } else if (MODE == MODE_TICK) {
+      } else if (kEp) {
         if (restart) {
-          restart_agent(s, init_word, v.maxT);
+          if (MODE == MODE_STREAM) {
+            // the next episode: its scenario's row over the lane's LDS row (the lazily applied
+            // mask is dropped with the old row), its teacher words, its init word
+            // (the teacher words first: their loads are in flight with the row's)
+            restart_from_entry(s, qe, v.maxT);
+            if (TL > 0) {
+              conn = v.pool_conn[s.scen];
+              if (v.ttab) {
+                tcw0 = v.tt_cells[2 * (size_t)s.scen];
+                tcw1 = v.tt_cells[2 * (size_t)s.scen + 1];
+              }
+            }
+            reload_grid_row<kReloadBatch>(reinterpret_cast<const uint4*>(v.pool + (size_t)s.scen * v.CS),
+                                          reinterpret_cast<uint32_t*>(g), v.CS);
+            v.init[slot] = qe.y;
+          } else {
+            restart_agent(s, init_word, v.maxT);
+          }
 #pragma unroll
           for (int w = 0; w < 8; ++w) { ivw[w] = 0u; m[w] = 0u; }
           inv_changed = mask_changed = true;
@@ -300,6 +358,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
         const int64_t i = env0 + tid;
         store_outputs(a, i, d, succ, counted);
         if (a.rec) a.rec[i] = counted ? act : -1;        // action_seqs, imitation.py:59-61
+        if (MODE == MODE_STREAM && a.ep_now) a.ep_now[i] = s.frozen ? -1 : cur;
         if (MODE == MODE_LANG && a.ask) a.ask[i] = (int8_t)(counted ? (a.bc && (bc & 0xffu)) : -1);
       }
     }
@@ -322,7 +381,8 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       // episode statistics: one partial-sum row per workgroup (uncontended)
       uint32_t n_succ = 0, n_end = 0, n_step = 0;
       tally_stats(live, counted, d, succ, n_succ, n_end, n_step);
-      const uint64_t bl = __ballot(live && counted && !d);
+      // (MODE_STREAM: a slot that restarted runs on, so the flag asks for slots not frozen)
+      const uint64_t bl = __ballot(MODE == MODE_STREAM ? (live && !s.frozen) : (live && counted && !d));
       if (tid == 0) {
         add_stats(v, (int64_t)blockIdx.x, n_succ, n_end, n_step);
         if (a.any_live && bl) *a.any_live = 1;          // idempotent plain store

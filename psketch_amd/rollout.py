@@ -137,14 +137,17 @@ def do_rollout(sim, spec, act, is_eval, behavior_clone=None, receive=None, keep_
         raise ValueError("lookahead needs is_eval or fused_teacher")
     # The teacher reads only the env states, so without the fused teacher tick t's labels are
     # computed on a side stream while the student's act(t) runs on the main stream.
-    main = torch.cuda.current_stream(dev)
+    # (the CPU variant, CraftSim(device="cpu"), runs every call synchronously: no streams)
+    main = None if sim._cpu else torch.cuda.current_stream(dev)
     side = None
     if not is_eval and not fused_teacher:
+        if sim._cpu:
+            raise ValueError("the CPU variant runs the fused teacher only (fused_teacher=True)")
         side = getattr(sim, "_teacher_stream", None)
         if side is None:                         # created once per simulator (costly)
             side = sim._teacher_stream = torch.cuda.Stream(dev)
     labels_ready = getattr(sim, "_teacher_event", None)
-    if labels_ready is None:
+    if labels_ready is None and not sim._cpu:
         labels_ready = sim._teacher_event = torch.cuda.Event()
 
     def launch_teacher(t):
@@ -214,10 +217,10 @@ def _stepper(sim, teach, bc, success):
     if bc is not None:
         args.behavior_clone = bc.data_ptr()
     args.success = success.data_ptr()
-    lib = N.lib()
+    lib = sim._L
     fn = lib.craft_step_teach if teach else lib.craft_step_ex
     h, pargs, di = sim._h, ctypes.byref(args), sim.device.index
-    raw = torch._C._cuda_getCurrentRawStream
+    raw = (lambda _: None) if sim._cpu else torch._C._cuda_getCurrentRawStream
 
     def step(t, actions, obs, ref, rec, live_ptr, labels):
         args.actions = actions.data_ptr()
@@ -228,7 +231,7 @@ def _stepper(sim, teach, bc, success):
         args.any_live = live_ptr
         st = fn(h, pargs, labels.data_ptr(), raw(di)) if teach else fn(h, pargs, raw(di))
         if st:
-            N.check(st, h, "craft_step_teach" if teach else "craft_step_ex")
+            N.check(st, h, "craft_step_teach" if teach else "craft_step_ex", L=lib)
     return step
 
 
@@ -380,7 +383,12 @@ def _live_flags(sim, T):
     device address (craft_host_flag_pointer) or 0 where HIP does not map it, and one event per
     tick."""
     flags = getattr(sim, "_live_host", None)
-    if flags is None or flags.numel() < T + 1:
+    if sim._cpu and (flags is None or flags.numel() < T + 1):
+        # the CPU variant's "device" memory is the host's, and its calls have completed on return
+        flags = sim._live_host = torch.zeros(max(T + 1, 64), dtype=torch.int32)
+        sim._live_events = [_NoEvent()] * flags.numel()
+        sim._live_dev = flags.data_ptr()
+    elif flags is None or flags.numel() < T + 1:
         flags = sim._live_host = torch.zeros(max(T + 1, 64), dtype=torch.int32, pin_memory=True)
         sim._live_events = [torch.cuda.Event() for _ in range(flags.numel())]
         p = ctypes.c_void_p()
@@ -388,6 +396,16 @@ def _live_flags(sim, T):
         sim._live_dev = p.value if ok and p.value else 0
     flags[:T + 1].zero_()
     return flags, sim._live_dev, sim._live_events
+
+
+class _NoEvent:
+    """The per-tick event of a simulator whose calls are synchronous (the CPU variant)."""
+
+    def record(self):
+        pass
+
+    def synchronize(self):
+        pass
 
 
 def _finish(sim, task, success, seqs, t, is_eval, keep_obs, obs_hist, timing, t_start, t_loop,
@@ -405,7 +423,7 @@ def _finish(sim, task, success, seqs, t, is_eval, keep_obs, obs_hist, timing, t_
     distances = torch.empty(n, dtype=torch.int32, device=dev)
     is_get = torch.empty(n, dtype=torch.uint8, device=dev)
     n_actions = torch.empty(n, dtype=torch.int32, device=dev)
-    sim._check(N.lib().craft_rollout_distances(
+    sim._check(sim._L.craft_rollout_distances(
         sim._h, task.data_ptr(), success.data_ptr(), seqs.data_ptr(), seqs.shape[0],
         distances.data_ptr(), is_get.data_ptr(), n_actions.data_ptr(), buf[3:4].data_ptr(),
         sim._stream()), "craft_rollout_distances")
@@ -434,6 +452,171 @@ def _finish(sim, task, success, seqs, t, is_eval, keep_obs, obs_hist, timing, t_
                        distances=distances, is_get=is_get, num_interactions=num_interactions,
                        num_steps=num_steps, ticks=t,
                        obs=obs_hist[:t + 1] if keep_obs else None)
+
+
+class EvalContext:
+    """What evaluate() hands the student beside the observations, int32 device tensors [n]:
+    episode (the queue index, i.e. the row of `specs`, each slot runs; -1 when the slot is
+    idle), tick (ticks into the slot's current episode) and restarted (1 for a slot that began
+    an episode since the last call: a recurrent student clears its state there)."""
+
+    def __init__(self, episode, tick, restarted):
+        self.episode, self.tick, self.restarted = episode, tick, restarted
+
+
+class EvalInfo:
+    """ImitationTrainer.evaluate's results (trainers/imitation.py:183-226): eval_info, the
+    reference's dict id -> {'actions', 'success'}; success_rate (per cent) and avg_distance
+    (get tasks only) as it logs them; and per instance, in the order of `specs`, host arrays:
+    success int8, n_actions int32, action_seqs int32 [count, max_timesteps] (-1 padded),
+    distances int32 (-1 where the task is not a get task), end_pose int32 [count, 3] (x, y,
+    dir of the final state); ticks = step launches of the pass."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def evaluate(sim, specs, act, ids=None, max_ticks=None):
+    """One pass over `specs` (ImitationTrainer.evaluate, trainers/imitation.py:183-226): every
+    instance is run once, in eval mode, and a slot that finishes one moves straight on to the
+    next (the episode queue, craft_step_stream) instead of idling until its batch is done.
+
+    specs: (scenario, x, y, dir, task) arrays, e.g. Dataset.specs(all instances), or int32
+      [count, 5] rows.  ids: the instances' ids (default: their indices).
+    act(obs, ctx) -> int device tensor [n]: obs is [n, F] on the device in the simulator's obs
+      format, overwritten by the next tick; ctx is an EvalContext.  Slot i's episodes are
+      specs rows i, i + n, i + 2n, ...: the assignment is static, so results do not depend on
+      timing.  The action of an idle slot is ignored (any value in 0..5).
+    max_ticks: a bound on the pass (default: ceil(count / n) * max_timesteps, which it cannot
+      exceed); RuntimeError if it ends with slots still running.
+    The failed get episodes' distances (imitation.py:83-91: find_closest_resources on the
+    initial grid at the final pose) are computed after the pass, n_envs at a time, with
+    set_state + teacher(path_len_out=): the simulator's slots are overwritten.
+    Raises RolloutError where the reference raises (success None; no reachable target)."""
+    n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
+    if isinstance(specs, (tuple, list)) and len(specs) == 5 and np.ndim(specs[0]) == 1:
+        specs = np.stack([np.asarray(torch.as_tensor(a).cpu()) for a in specs], 1)
+    specs = np.ascontiguousarray(np.asarray(torch.as_tensor(specs).cpu()), dtype=np.int32)
+    if specs.ndim != 2 or specs.shape[1] != 5 or len(specs) == 0:
+        raise ValueError("specs must be [count >= 1, 5]")
+    count = len(specs)
+    ids = list(range(count)) if ids is None else list(ids)
+    if len(ids) != count:
+        raise ValueError(f"{len(ids)} ids for {count} specs")
+    # every slot needs a first entry: a short split is padded with copies of its first row,
+    # whose episodes are dropped
+    queue = specs if count >= n else np.concatenate([specs, np.repeat(specs[:1], n - count, 0)])
+    rounds = (len(queue) + n - 1) // n
+    bound = rounds * T
+    max_ticks = bound if max_ticks is None else min(int(max_ticks), bound)
+    sim.set_episode_queue(torch.as_tensor(queue))
+    obs = sim.empty_obs()
+    sim.begin_episodes(first=0, stride=n, wrap=False, obs=obs)
+    i32 = dict(dtype=torch.int32, device=dev)
+    rec = torch.full((max_ticks, n), -1, **i32)
+    ended = torch.full((max_ticks, n), -1, **i32)
+    pose = torch.full((max_ticks, n), -1, **i32)
+    succ = torch.full((max_ticks, n), -1, dtype=torch.int8, device=dev)
+    now = torch.empty(n, **i32)
+    ctx = EvalContext(torch.arange(n, **i32), torch.zeros(n, **i32), torch.ones(n, **i32))
+    flags, flag_dev, events = _live_flags(sim, max_ticks)
+    live = None if flag_dev else torch.zeros(max_ticks + 1, **i32)
+    args = N.craft_stream_step_args_t()
+    args.step.flags = N.STEP_AUTORESET
+    args.step.obs = obs.data_ptr()
+    args.episode_now = now.data_ptr()
+    fn, h, pargs = sim._L.craft_step_stream, sim._h, ctypes.byref(args)
+    t = 0
+    running = True
+    while running and t < max_ticks:
+        actions = act(obs, ctx)
+        if not torch.is_tensor(actions):
+            actions = torch.as_tensor(np.asarray(actions), device=dev)
+        actions = actions.to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+        args.step.actions = actions.data_ptr()
+        args.step.tick = t
+        args.step.success = succ[t].data_ptr()
+        args.step.action_record = rec[t].data_ptr()
+        args.step.any_live = flag_dev + 4 * t if flag_dev else live[t].data_ptr()
+        args.episode_end = ended[t].data_ptr()
+        args.end_pose = pose[t].data_ptr()
+        st = fn(h, pargs, sim._stream())
+        if st:
+            N.check(st, h, "craft_step_stream", L=sim._L)
+        # the next call's context, on the device
+        began = ended[t] >= 0
+        ctx = EvalContext(now.clone(), torch.where(began, 0, ctx.tick + 1).to(torch.int32),
+                          (began & (now >= 0)).to(torch.int32))
+        if not flag_dev:
+            flags[t:t + 1].copy_(live[t:t + 1], non_blocking=True)
+        events[t].record()
+        events[t].synchronize()
+        running = int(flags[t]) != 0
+        t += 1
+    if running:
+        raise RuntimeError(f"evaluate: slots still running after {t} ticks")
+    sim.check()                                  # an error latched during the pass
+    return _eval_summary(sim, specs, ids, rec[:t].cpu().numpy(), ended[:t].cpu().numpy(),
+                         pose[:t].cpu().numpy(), succ[:t].cpu().numpy(), t)
+
+
+def _eval_summary(sim, specs, ids, rec, ended, pose, succ, ticks):
+    """evaluate()'s per-instance results from the pass's per-tick records ([ticks, n] each: the
+    action taken, the queue index of an episode that ended, its final pose and success)."""
+    n, T, count = sim.n_envs, sim.config.max_timesteps, len(specs)
+    seqs = np.full((count, T), -1, dtype=np.int32)
+    n_actions = np.zeros(count, dtype=np.int32)
+    success = np.full(count, -2, dtype=np.int8)          # -2: never finished
+    end_pose = np.zeros((count, 3), dtype=np.int32)
+    # slot i runs episodes i, i + n, ... in order: cut its action column at its episode ends
+    tt, ii = np.nonzero(ended >= 0)
+    start = np.zeros(n, dtype=np.int64)
+    for t, i in zip(tt, ii):                             # (np.nonzero: tick-major, so in order per slot)
+        e = ended[t, i]
+        if e < count:
+            a = rec[start[i]:t + 1, i]
+            seqs[e, :len(a)] = a
+            n_actions[e] = len(a)
+            success[e] = succ[t, i]
+            p = pose[t, i]
+            end_pose[e] = (p & 0xff, (p >> 8) & 0xff, (p >> 16) & 3)
+        start[i] = t + 1
+    if (success == -2).any():
+        raise RuntimeError(f"evaluate: instance {int(np.argmax(success == -2))} was never finished")
+    if (success < 0).any():
+        raise RolloutError("satisfies() returned None for a finished episode (imitation.py:68)")
+    goals = np.asarray([t.goal_name == "get" for t in sim.task_manager.tasks])
+    is_get = goals[specs[:, 4]]
+    distances = np.where(is_get, 0, -1).astype(np.int32)
+    failed = np.nonzero(is_get & (success == 0))[0]
+    K = sim.n_kinds
+    for lo in range(0, len(failed), n):
+        idx = failed[lo:lo + n]
+        m = len(idx)
+        slots = torch.arange(m, dtype=torch.int32, device=sim.device)
+        agent = np.concatenate([end_pose[idx], np.full((m, 1), T, dtype=np.int32)], 1)
+        sim.set_state(torch.as_tensor(specs[idx]), torch.as_tensor(agent),
+                      torch.zeros((m, K), dtype=torch.int32), slots=slots)
+        plen = torch.empty(m, dtype=torch.int32, device=sim.device)
+        sim.teacher(slots=slots, path_len_out=plen)
+        distances[idx] = plen.cpu().numpy()
+    if len(failed):
+        try:                                     # the probes' own labels may raise where the
+            sim.check()                          # reference never asks: only the lengths count
+        except N.CraftError as e:
+            if e.status != N.ETEACHER:
+                raise
+    if (distances[failed] < 0).any():
+        raise RolloutError("find_closest_resources found no target: len(None) (imitation.py:88-89)")
+    eval_info = {ids[e]: {"actions": [int(a) for a in seqs[e, :n_actions[e]]], "success": int(success[e])}
+                 for e in range(count)}
+    if len(eval_info) != count:
+        raise ValueError("ids are not unique (imitation.py:203)")
+    get_d = distances[is_get]
+    return EvalInfo(eval_info=eval_info, success_rate=int(success.sum()) / count * 100,
+                    avg_distance=(int(get_d.sum()) / len(get_d)) if len(get_d) else float("nan"),
+                    success=success, n_actions=n_actions, action_seqs=seqs, distances=distances,
+                    is_get=is_get, end_pose=end_pose, ticks=ticks)
 
 
 class ImitationRollout:
@@ -474,3 +657,11 @@ class ImitationRollout:
             bc = self.random.binomial(1, self.policy_mix_rate, size=len(batch))
         return do_rollout(sim, spec, act, is_eval, behavior_clone=bc, receive=receive,
                           keep_obs=keep_obs)
+
+    def evaluate(self, dataset, act, n_envs=32):
+        """ImitationTrainer.evaluate(dataset, ...) (trainers/imitation.py:183-226): one pass
+        over every instance of `dataset` (a Dataset, or any sequence of its items) on a
+        simulator of n_envs slots; see evaluate().  Returns an EvalInfo."""
+        from .dataset import Dataset
+        items = list(dataset)
+        return evaluate(self.sim(n_envs), Dataset.specs(items), act, ids=[it["id"] for it in items])

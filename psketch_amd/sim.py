@@ -378,6 +378,80 @@ class CraftSim:
                     "craft_step_lang")
         return obs
 
+    # ---- the episode queue ------------------------------------------------------------
+    def set_episode_queue(self, specs):
+        """Install the episode queue (craft_episode_queue): specs is int32 [count, 5] rows of
+        (scenario, x0, y0, dir0, task), or the 5-tuple of arrays Dataset.specs returns.  Every
+        entry is checked on the device; an invalid one raises (EINVAL, naming the first) and
+        the queue installed before stays.  Synchronous."""
+        if isinstance(specs, (tuple, list)) and len(specs) == 5 and not np.isscalar(specs[0]) \
+                and np.ndim(specs[0]) == 1:
+            specs = np.stack([np.asarray(torch.as_tensor(a).cpu()) for a in specs], 1)
+        q = torch.as_tensor(specs)
+        if q.dim() != 2 or q.shape[1] != 5:
+            raise ValueError(f"specs must be [count, 5], got {tuple(q.shape)}")
+        q = q.to(device=self.device, dtype=torch.int32).contiguous()
+        self._check(self._L.craft_episode_queue(self._h, _ptr(q), int(q.shape[0])),
+                    "craft_episode_queue")
+        self.queue_count = int(q.shape[0])
+
+    def begin_episodes(self, first=0, stride=None, wrap=False, obs=None):
+        """Put every slot on its first queue entry (craft_episode_begin): the slot with global
+        id g = env_id_base + i starts on entry first + g and later takes first + g + k * stride
+        (stride: default n_envs; the total envs of all ranks when sharded).  wrap: indices mod
+        count, so the stream never runs out; else a slot past the end freezes.  obs as reset."""
+        stride = self.n_envs if stride is None else int(stride)
+        self._check(self._L.craft_episode_begin(self._h, int(first), stride,
+                                                N.QUEUE_WRAP if wrap else 0, self._obs(obs),
+                                                self._stream()), "craft_episode_begin")
+        return obs
+
+    def step_stream(self, actions=None, seed=0, tick=0, obs=None, reward=None, done=None,
+                    success=None, ref_actions=None, behavior_clone=None, action_record=None,
+                    any_live=None, transition_code=None, labels=None, episode_end=None,
+                    end_pose=None, episode_now=None):
+        """step(autoreset=True) whose restart takes the slot's next queue entry
+        (craft_step_stream), with three more int32 [N] outputs: episode_end (the queue index of
+        the episode that ended this tick, else -1), end_pose (x | y << 8 | dir << 16 of its
+        final state, else -1) and episode_now (the queue index the slot runs after the tick, -1
+        once it has run out).  any_live: some slot is still running after the tick."""
+        n = self.n_envs
+        args = N.craft_stream_step_args_t()
+        keep = []
+
+        def put(struct, field, t):
+            if t is not None:
+                keep.append(t)
+                setattr(struct, field, t.data_ptr())
+
+        st = args.step
+        put(st, "actions", self._i32(actions, n) if actions is not None else None)
+        put(st, "ref_actions", self._i32(ref_actions, n) if ref_actions is not None else None)
+        if behavior_clone is not None:
+            bc = torch.as_tensor(behavior_clone, device=self.device)
+            bc = (bc != 0).to(torch.uint8).contiguous() if bc.dtype != torch.uint8 else bc.contiguous()
+            if bc.numel() != n:
+                raise ValueError(f"behavior_clone: expected {n} entries")
+            put(st, "behavior_clone", bc)
+        for name, t, dt, shape in (("reward", reward, torch.float32, (n,)),
+                                   ("done", done, torch.uint8, (n,)),
+                                   ("success", success, torch.int8, (n,)),
+                                   ("action_record", action_record, torch.int32, (n,)),
+                                   ("any_live", any_live, torch.int32, (1,)),
+                                   ("transition_code", transition_code, torch.int8, (n,))):
+            put(st, name, self._buf(name, t, dt, shape))
+        self._obs(obs)
+        put(st, "obs", obs)
+        st.action_seed = seed & (2**64 - 1)
+        st.tick = int(tick)
+        st.flags = N.STEP_AUTORESET
+        for name, t in (("label_out", labels), ("episode_end", episode_end),
+                        ("end_pose", end_pose), ("episode_now", episode_now)):
+            put(args, name, self._buf(name, t, torch.int32, (n,)))
+        self._check(self._L.craft_step_stream(self._h, ctypes.byref(args), self._stream()),
+                    "craft_step_stream")
+        return obs
+
     def rollout(self, n_ticks, seed=0, tick0=0, actions=None, autoreset=True, obs=None,
                 reward=None, done=None, success=None):
         """n_ticks craft_step ticks in one launch (include/craft.h craft_rollout),
