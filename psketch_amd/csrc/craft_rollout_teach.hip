@@ -2,6 +2,7 @@
 // (craft_rollout_teach.h), one instantiation per window and BFS word count.
 #include <algorithm>
 
+#include "craft_launch.h"
 #include "craft_rollout_teach.h"
 
 namespace craft {

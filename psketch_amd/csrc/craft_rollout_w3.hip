@@ -1,5 +1,6 @@
 // craft_rollout_w3.hip — rollout_kernel instantiations for 3x3 windows
 // (one translation unit per window so the build compiles them in parallel).
+#include "craft_launch.h"
 #include "craft_rollout.h"
 
 namespace craft {

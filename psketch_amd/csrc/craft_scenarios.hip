@@ -22,6 +22,7 @@
 // scenario stream bit for bit (tests/test_oracle_golden.py), with splitmix64 it
 // is the parity check of this kernel.
 #include "craft_bits.h"
+#include "craft_launch.h"
 
 namespace craft {
 

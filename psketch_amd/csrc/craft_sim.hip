@@ -2,8 +2,9 @@
 // scenario pool, launches, state I/O and episode statistics.
 // Kernels: craft_tile.hip (tick / transition / observe / reset), craft_tick_lang.hip (the
 // language trainers' tick), craft_tick_stream.hip (the episode queue and its tick),
-// craft_rollout.hip (multi-tick), craft_teacher.hip,
-// craft_scenarios.hip (pool generation).
+// craft_tick_teach.hip (the tick fused with the teacher), craft_rollout_w3/w5/w7.hip (multi-tick),
+// craft_rollout_teach.hip (multi-tick with labels), craft_teacher.hip, craft_scenarios.hip (pool
+// generation).  Their launchers: craft_launch.h.
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -13,34 +14,9 @@
 
 #include "craft_device.h"
 #include "craft_host.h"
+#include "craft_launch.h"
 
 namespace craft {
-hipError_t launch_tile(int mode, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                       hipStream_t st);
-hipError_t launch_teacher(int nw, int lanes, const SimView& v, const int32_t* slots, const int32_t* tasks,
-                          int64_t n, int32_t* act_out, int32_t* len_out, hipStream_t st);
-hipError_t launch_rollout_teach(int win, int nw, const SimView& v, const RolloutArgs& a, hipStream_t st);
-hipError_t launch_distances(int nw, const SimView& v, const int32_t* tasks, const int8_t* success,
-                            const int32_t* seqs, int32_t ticks, int64_t n, int32_t* dist_out,
-                            uint8_t* is_get_out, int32_t* n_actions_out, int32_t* flags, hipStream_t st);
-hipError_t launch_rollout(int win, int tile, int threads, const SimView& v, const RolloutArgs& a, size_t lds,
-                          hipStream_t st);
-hipError_t launch_scenarios(const SimView& v, const ScenarioArgs& a, hipStream_t st);
-hipError_t launch_tick_teach(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                             hipStream_t st);
-hipError_t launch_tick2(int tl, int nw, const SimView& v, const TileArgs& a, size_t lds, hipStream_t st);
-hipError_t launch_tick_lang(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                            hipStream_t st);
-hipError_t launch_tick_stream(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                              hipStream_t st);
-hipError_t launch_queue_pack(const SimView& v, const int32_t* specs, int64_t count, uint2* out,
-                             unsigned long long* first_bad, hipStream_t st);
-hipError_t launch_queue_begin(const uint2* entries, int64_t count, int64_t first_gid, int wrap, int64_t n,
-                              int32_t* cursor, int32_t* r, hipStream_t st);
-size_t tick2_lds_bytes(int tl, int nw, int GS, int F);
-hipError_t launch_teach_table(int nw, const SimView& v, int32_t first, int32_t count, const int32_t* kinds,
-                              hipStream_t st);
-
 namespace {
 
 __global__ void get_state_kernel(SimView v, const int32_t* slots, int64_t n, int32_t* agent_out,
@@ -231,23 +207,13 @@ int default_tile(int win) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// LDS bytes per tile workgroup; a residency cap R pads the request to 160 KiB / R
+// LDS bytes per tile workgroup (the tile kernel's, craft_tile.h, or with two observation buffers and
+// the pristine rows the rollout kernels'); a residency cap R pads the request to 160 KiB / R
 // so that at most R tile workgroups share a CU and later tiles' prologues overlap
 // earlier tiles' observation stores.
 size_t lds_bytes(const craft_sim* s, int tile, int obs_bufs = 1, bool pristine = false) {
   const SimView& v = s->view;
   size_t b = (size_t)craft::lds_layout(tile, v.GS, v.F, obs_bufs, pristine).bytes;
-  if (s->resident_cap > 0) {
-    const size_t capped = ((size_t)163840 / s->resident_cap) & ~size_t(15);
-    if (capped > b) b = capped;
-  }
-  return b;
-}
-
-// The tile kernel's (craft_tile.h).
-size_t tile_lds_bytes(const craft_sim* s, int tile) {
-  const SimView& v = s->view;
-  size_t b = (size_t)craft::lds_layout(tile, v.GS, v.F).bytes;
   if (s->resident_cap > 0) {
     const size_t capped = ((size_t)163840 / s->resident_cap) & ~size_t(15);
     if (capped > b) b = capped;
@@ -353,10 +319,85 @@ SimView teach_view(const craft_sim* s) {
   return v;
 }
 
+// What one tick of the tile kernel launches with: the view, teacher lanes per env (0: no teacher in
+// the launch), words per BFS cell set, envs per tile and LDS bytes.
+struct TickPlan {
+  SimView v;
+  int tl, nw, tile;
+  size_t lds;
+};
+
+// The plan of `what`'s tick.  Bare: the handle's view and tile, the LDS padded by the residency
+// cap.  With the teacher (craft_step_teach's one-tile kernel: its tile, its lanes, its LDS, never
+// padded): the table entries of newly loaded rows are built first (flush_table), and the two-tile
+// kernel takes the view and nw from here and sizes its own LDS.
+int tick_plan(craft_sim* s, bool teach, void* stream, const char* what, TickPlan& p) {
+  if (!teach) {
+    p = TickPlan{s->view, 0, 0, s->tile, lds_bytes(s, s->tile)};
+    return CRAFT_OK;
+  }
+  const int rc = flush_table(s, stream, what);
+  if (rc != CRAFT_OK) return rc;
+  // Teacher-table reads in the fused kernel (its 4-bit copy since round 5): -2.5 us per tick when
+  // the launch rewrites the previous launch's observation buffer (a trainer's loop, ring 1), and
+  // -0.9 us (30.1 -> 29.2) when every launch writes a fresh slot of a 16-slot ring (round 6,
+  // profiles/r06/teach_table_k1; round 4's u16 reads cost +0.5 us there), so auto reads it always.
+  p.v = teach_view(s);
+  p.v.tt_fused = s->teach_table != 2;
+  p.tl = one_tile_lanes(s);
+  p.nw = craft::teach_words(s->view.W, s->view.H);
+  p.tile = teach_tile(s);
+  // + task_sub as bytes (the teacher's other words live in row padding and the control words,
+  // craft_tile.h): 40,888 bytes for a 32-env tile at 12x12, 5x5, so four workgroups share a CU
+  p.lds = (size_t)craft::lds_layout(p.tile, s->view.GS, s->view.F).bytes +
+          (((size_t)s->view.n_tasks * CRAFT_MAX_SUBTASKS + 15) & ~size_t(15));
+  return CRAFT_OK;
+}
+
 int launch(craft_sim* s, int mode, const TileArgs& a, void* stream, const char* what) {
-  hipError_t e = craft::launch_tile(mode, s->cfg.window_width, s->tile, s->view, a, tile_lds_bytes(s, s->tile),
+  hipError_t e = craft::launch_tile(mode, s->cfg.window_width, s->tile, s->view, a, lds_bytes(s, s->tile),
                                     reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(s, e, what);
+  return CRAFT_OK;
+}
+
+// The teachers refuse grids whose BFS would overflow the reference's 1000-state queue.
+int check_bfs_queue(craft_sim* s, const char* what) {
+  if (4 * s->view.C <= 1000) return CRAFT_OK;
+  return fail(s, CRAFT_EINVAL, std::string(what) + ": 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+}
+
+// Every slot of a rollout's observation ring starts 16-byte aligned (no ring: nothing to check).
+bool ring_slots_aligned(const craft_sim* s, const void* obs, int ring) {
+  const int64_t slot = s->n_envs * (int64_t)s->view.F * craft::obs_elem_bytes(s->view.obs_fmt);
+  return !obs || (aligned16(obs) && (ring <= 1 || slot % 16 == 0));
+}
+
+// The sync area of a rollout launch of a.n_ticks ticks on `st`: a.queue, a.tile_done and the
+// counters' values at its start (a.qbase, a.qbase1); `captured` says whether it is being captured.
+// A launch captured into a HIP graph (torch.cuda.graph) is replayed without this host code, so
+// it cannot use the eager launches' running counter: it gets its own sync area, zeroed by a
+// memset captured with it, so every replay starts from zero and never touches the eager one.
+// The eager area is zeroed once and then its counters only grow: a launch hands out units
+// counter - qbase and ends having added what its caller records in queue_next / queue1_next.
+// `rezero`: the launch also needs zeroed per-tile flags, so the whole area is zeroed again.
+int rollout_sync(craft_sim* s, hipStream_t st, bool rezero, craft::RolloutArgs& a, bool& captured) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIP_TRY(s, hipStreamIsCapturing(st, &cap));
+  captured = cap != hipStreamCaptureStatusNone;
+  uint8_t* sync = captured ? s->d_sync_graph : s->d_sync;
+  a.queue = reinterpret_cast<unsigned long long*>(sync);
+  a.tile_done = reinterpret_cast<uint32_t*>(sync + 16);
+  if (a.n_ticks > 0 && (captured || rezero || !s->sync_zeroed)) {
+    HIP_TRY(s, hipMemsetAsync(sync, 0, s->sync_bytes, st));
+    if (!captured) {
+      s->sync_zeroed = true;
+      s->queue_next = 0;
+      s->queue1_next = 0;
+    }
+  }
+  a.qbase = captured ? 0 : s->queue_next;
+  a.qbase1 = captured ? 0 : s->queue1_next;
   return CRAFT_OK;
 }
 
@@ -899,37 +940,21 @@ int step_args(craft_sim_t* s, const craft_step_args_t* x, TileArgs& a) {
 
 int craft_step_teach(craft_sim_t* s, const craft_step_args_t* x, int32_t* label_out, void* stream) {
   if (!s || !x || !label_out) return CRAFT_EINVAL;
-  if (4 * s->view.C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_step_teach: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  int rc = check_bfs_queue(s, "craft_step_teach");
+  if (rc != CRAFT_OK) return rc;
   TileArgs a;
-  const int rc = step_args(s, x, a);
+  rc = step_args(s, x, a);
   if (rc != CRAFT_OK) return rc;
   a.label = label_out;
   int kernel = 0, envs = 0, tl = 0;
   step_shape(s, true, &kernel, &envs, &tl);
-  const int nw = craft::teach_words(s->view.W, s->view.H);
+  TickPlan p;
+  rc = tick_plan(s, true, stream, "craft_step_teach", p);
+  if (rc != CRAFT_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e;
-  // Teacher-table reads in the fused kernel (its 4-bit copy since round 5): -2.5 us per tick when
-  // the launch rewrites the previous launch's observation buffer (a trainer's loop, ring 1), and
-  // -0.9 us (30.1 -> 29.2) when every launch writes a fresh slot of a 16-slot ring (round 6,
-  // profiles/r06/teach_table_k1; round 4's u16 reads cost +0.5 us there), so auto reads it always.
-  {
-    const int frc = flush_table(s, stream, "craft_step_teach");
-    if (frc != CRAFT_OK) return frc;
-  }
-  SimView v = teach_view(s);
-  v.tt_fused = s->teach_table != 2;
-  if (kernel == 2) {
-    e = craft::launch_tick2(tl, nw, v, a, craft::tick2_lds_bytes(tl, nw, s->view.GS, s->view.F), st);
-  } else {
-    const int tile = teach_tile(s);
-    // + task_sub as bytes (the teacher's other words live in row padding and the control words,
-    // craft_tile.h): 40,888 bytes for a 32-env tile at 12x12, 5x5, so four workgroups share a CU
-    const size_t lds = (size_t)craft::lds_layout(tile, s->view.GS, s->view.F).bytes +
-                       (((size_t)s->view.n_tasks * CRAFT_MAX_SUBTASKS + 15) & ~size_t(15));
-    e = craft::launch_tick_teach(tl, nw, s->cfg.window_width, tile, v, a, lds, st);
-  }
+  const hipError_t e =
+      kernel == 2 ? craft::launch_tick2(tl, p.nw, p.v, a, craft::tick2_lds_bytes(tl, p.nw, s->view.GS, s->view.F), st)
+                  : craft::launch_tick_teach(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds, st);
   if (e != hipSuccess) return hip_fail(s, e, "craft_step_teach launch");
   return CRAFT_OK;
 }
@@ -939,8 +964,8 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* strea
   if (x->flags != 0) return fail(s, CRAFT_EINVAL, "craft_step_lang: flags must be 0 (no auto-reset in this protocol)");
   if (x->use_alt && !x->alt_actions) return fail(s, CRAFT_EINVAL, "craft_step_lang: use_alt needs alt_actions");
   if (x->obs && !aligned16(x->obs)) return fail(s, CRAFT_EINVAL, "craft_step_lang: obs must be 16-byte aligned");
-  if (x->label_out && 4 * s->view.C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_step_lang: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  int rc = x->label_out ? check_bfs_queue(s, "craft_step_lang") : CRAFT_OK;
+  if (rc != CRAFT_OK) return rc;
   TileArgs a{};
   a.actions = x->actions;
   a.ref = x->alt_actions;
@@ -956,22 +981,11 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* strea
   a.code = x->transition_code;
   a.any_live = x->any_live;
   a.label = x->label_out;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (!x->label_out) {
-    e = craft::launch_tick_lang(0, 0, s->cfg.window_width, s->tile, s->view, a, tile_lds_bytes(s, s->tile), st);
-  } else {
-    const int frc = flush_table(s, stream, "craft_step_lang");
-    if (frc != CRAFT_OK) return frc;
-    SimView v = teach_view(s);
-    v.tt_fused = s->teach_table != 2;
-    // the one-tile kernel in craft_step_teach's shape: its tile, its lanes, its LDS
-    const int tile = teach_tile(s);
-    const size_t lds = (size_t)craft::lds_layout(tile, s->view.GS, s->view.F).bytes +
-                       (((size_t)s->view.n_tasks * CRAFT_MAX_SUBTASKS + 15) & ~size_t(15));
-    e = craft::launch_tick_lang(one_tile_lanes(s), craft::teach_words(s->view.W, s->view.H), s->cfg.window_width, tile,
-                                v, a, lds, st);
-  }
+  TickPlan p;
+  rc = tick_plan(s, x->label_out != nullptr, stream, "craft_step_lang", p);
+  if (rc != CRAFT_OK) return rc;
+  const hipError_t e = craft::launch_tick_lang(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
+                                               reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(s, e, "craft_step_lang launch");
   return CRAFT_OK;
 }
@@ -1061,10 +1075,10 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* s
     return fail(s, CRAFT_EINVAL, "craft_step_stream: step.flags must be CRAFT_STEP_AUTORESET");
   if (!s->d_queue || !s->q_begun)
     return fail(s, CRAFT_EINVAL, "craft_step_stream: craft_episode_begin has not put the slots on the queue");
-  if (x->label_out && 4 * s->view.C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_step_stream: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  int rc = x->label_out ? check_bfs_queue(s, "craft_step_stream") : CRAFT_OK;
+  if (rc != CRAFT_OK) return rc;
   TileArgs a;
-  const int rc = step_args(s, &x->step, a);
+  rc = step_args(s, &x->step, a);
   if (rc != CRAFT_OK) return rc;
   a.label = x->label_out;
   a.q_entries = s->d_queue;
@@ -1075,22 +1089,11 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* s
   a.ep_end = x->episode_end;
   a.end_pose = x->end_pose;
   a.ep_now = x->episode_now;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (!x->label_out) {
-    e = craft::launch_tick_stream(0, 0, s->cfg.window_width, s->tile, s->view, a, tile_lds_bytes(s, s->tile), st);
-  } else {
-    const int frc = flush_table(s, stream, "craft_step_stream");
-    if (frc != CRAFT_OK) return frc;
-    SimView v = teach_view(s);
-    v.tt_fused = s->teach_table != 2;
-    // the one-tile kernel in craft_step_teach's shape: its tile, its lanes, its LDS
-    const int tile = teach_tile(s);
-    const size_t lds = (size_t)craft::lds_layout(tile, s->view.GS, s->view.F).bytes +
-                       (((size_t)s->view.n_tasks * CRAFT_MAX_SUBTASKS + 15) & ~size_t(15));
-    e = craft::launch_tick_stream(one_tile_lanes(s), craft::teach_words(s->view.W, s->view.H), s->cfg.window_width,
-                                  tile, v, a, lds, st);
-  }
+  TickPlan p;
+  rc = tick_plan(s, x->label_out != nullptr, stream, "craft_step_stream", p);
+  if (rc != CRAFT_OK) return rc;
+  const hipError_t e = craft::launch_tick_stream(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
+                                                 reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(s, e, "craft_step_stream launch");
   return CRAFT_OK;
 }
@@ -1109,8 +1112,7 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
   if (!s) return CRAFT_EINVAL;
   if (n_ticks < 0 || ring < 1 || tick0 < 0)
     return fail(s, CRAFT_EINVAL, "craft_rollout: need n_ticks >= 0, ring >= 1, tick0 >= 0");
-  const int esz = craft::obs_elem_bytes(s->view.obs_fmt);
-  if (obs && (!aligned16(obs) || (ring > 1 && (s->n_envs * (int64_t)s->view.F * esz) % 16 != 0)))
+  if (!ring_slots_aligned(s, obs, ring))
     return fail(s, CRAFT_EINVAL, "craft_rollout: every obs ring slot must be 16-byte aligned");
   craft::RolloutArgs a{};
   a.actions = actions;
@@ -1125,15 +1127,6 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
   a.sat = success;
   a.chunk = s->rollout_chunk > 0 ? s->rollout_chunk : (n_ticks > 0 ? n_ticks : 1);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // A launch captured into a HIP graph (torch.cuda.graph) is replayed without this host code, so
-  // it cannot use the eager launches' running counter: it gets its own sync area, zeroed by a
-  // memset captured with it, so every replay starts from zero and never touches the eager one.
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIP_TRY(s, hipStreamIsCapturing(st, &cap));
-  const bool captured = cap != hipStreamCaptureStatusNone;
-  uint8_t* sync = captured ? s->d_sync_graph : s->d_sync;
-  a.queue = reinterpret_cast<unsigned long long*>(sync);
-  a.tile_done = reinterpret_cast<uint32_t*>(sync + 16);
   int tile = 0, threads = 0, split = 0;
   rollout_shape(s, &tile, &threads, &split);
   // chunk_ticks -1: the split kernel's continuous pipeline (its 3x3 default shape, observations
@@ -1141,25 +1134,12 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
   const bool flat = s->rollout_chunk == -1 && split && tile == 32 && threads == 512 &&
                     s->cfg.window_width == 3 && obs != nullptr;
   a.flat = flat ? 1 : 0;
-  // The work-unit counter is zeroed once and then only grows: a launch hands out units
-  // counter - qbase and ends having added its units + its grid.  Chunked launches (tiles
-  // handed between workgroups) also need zeroed per-tile flags: those zero the whole area.
+  // Chunked launches (tiles handed between workgroups) need zeroed per-tile flags.
   const int64_t n_chunks = n_ticks > 0 ? (n_ticks + a.chunk - 1) / a.chunk : 0;
   const int64_t units = ((s->n_envs + tile - 1) / tile) * n_chunks;
-  if (captured) {
-    if (n_ticks > 0) HIP_TRY(s, hipMemsetAsync(sync, 0, s->sync_bytes, st));
-    a.qbase = 0;
-    a.qbase1 = 0;
-  } else {
-    if (n_ticks > 0 && (n_chunks > 1 || !s->sync_zeroed)) {
-      HIP_TRY(s, hipMemsetAsync(s->d_sync, 0, s->sync_bytes, st));
-      s->sync_zeroed = true;
-      s->queue_next = 0;
-      s->queue1_next = 0;
-    }
-    a.qbase = s->queue_next;
-    a.qbase1 = s->queue1_next;
-  }
+  bool captured = false;
+  const int rc = rollout_sync(s, st, n_chunks > 1, a, captured);
+  if (rc != CRAFT_OK) return rc;
   int64_t grid = 0;
   a.grid_out = &grid;
   SimView view = s->view;
@@ -1178,13 +1158,12 @@ int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, voi
   if (!s || !x) return CRAFT_EINVAL;
   if (x->n_ticks < 0 || x->ring < 1 || x->tick0 < 0)
     return fail(s, CRAFT_EINVAL, "craft_rollout_teach: need n_ticks >= 0, ring >= 1, tick0 >= 0");
-  if (4 * s->view.C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_rollout_teach: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  int rc = check_bfs_queue(s, "craft_rollout_teach");
+  if (rc != CRAFT_OK) return rc;
   const bool lsync = x->label_actions != 0 || x->behavior_clone != nullptr;
   if (lsync && !x->label_in)
     return fail(s, CRAFT_EINVAL, "craft_rollout_teach: label_actions / behavior_clone need label_in");
-  const int esz = craft::obs_elem_bytes(s->view.obs_fmt);
-  if (x->obs && (!aligned16(x->obs) || (x->ring > 1 && (s->n_envs * (int64_t)s->view.F * esz) % 16 != 0)))
+  if (!ring_slots_aligned(s, x->obs, x->ring))
     return fail(s, CRAFT_EINVAL, "craft_rollout_teach: every obs ring slot must be 16-byte aligned");
   if (x->n_ticks == 0) return CRAFT_OK;
   craft::RolloutArgs a{};
@@ -1208,33 +1187,14 @@ int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, voi
   a.use_table = s->teach_table != 2;              // auto = always: the reads overlap the stream
   a.labels = x->labels;
   a.rec = x->action_record;
-  {
-    const int frc = flush_table(s, stream, "craft_rollout_teach");
-    if (frc != CRAFT_OK) return frc;
-  }
+  rc = flush_table(s, stream, "craft_rollout_teach");
+  if (rc != CRAFT_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // the work-unit counter as craft_rollout's split kernel uses it (queue[1], one claim past the
-  // last unit per workgroup); a captured launch gets the graph's own zeroed counter
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIP_TRY(s, hipStreamIsCapturing(st, &cap));
-  const bool captured = cap != hipStreamCaptureStatusNone;
-  uint8_t* sync = captured ? s->d_sync_graph : s->d_sync;
-  a.queue = reinterpret_cast<unsigned long long*>(sync);
-  a.tile_done = reinterpret_cast<uint32_t*>(sync + 16);
-  if (captured) {
-    HIP_TRY(s, hipMemsetAsync(sync, 0, s->sync_bytes, st));
-    a.qbase = 0;
-    a.qbase1 = 0;
-  } else {
-    if (!s->sync_zeroed) {
-      HIP_TRY(s, hipMemsetAsync(s->d_sync, 0, s->sync_bytes, st));
-      s->sync_zeroed = true;
-      s->queue_next = 0;
-      s->queue1_next = 0;
-    }
-    a.qbase = s->queue_next;
-    a.qbase1 = s->queue1_next;
-  }
+  // last unit per workgroup)
+  bool captured = false;
+  rc = rollout_sync(s, st, false, a, captured);
+  if (rc != CRAFT_OK) return rc;
   int64_t grid = 0;
   a.grid_out = &grid;
   SimView v = teach_view(s);
@@ -1295,15 +1255,13 @@ int craft_rollout_distances(craft_sim_t* s, const int32_t* tasks, const int8_t* 
   if (!tasks || !success || !distances_out || !is_get_out || !n_actions_out || !flags_out || ticks < 0 ||
       (ticks > 0 && !action_seqs))
     return fail(s, CRAFT_EINVAL, "craft_rollout_distances: bad argument");
-  if (4 * s->view.C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_rollout_distances: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  int rc = check_bfs_queue(s, "craft_rollout_distances");
+  if (rc != CRAFT_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   HIP_TRY(s, hipMemsetAsync(flags_out, 0, 2 * sizeof(int32_t), st));
   if (s->n_envs == 0) return CRAFT_OK;
-  {
-    const int frc = flush_table(s, stream, "craft_rollout_distances");
-    if (frc != CRAFT_OK) return frc;
-  }
+  rc = flush_table(s, stream, "craft_rollout_distances");
+  if (rc != CRAFT_OK) return rc;
   hipError_t e = craft::launch_distances(craft::teach_words(s->view.W, s->view.H), teach_view(s), tasks, success, action_seqs, ticks,
                                          s->n_envs, distances_out, is_get_out, n_actions_out, flags_out, st);
   if (e != hipSuccess) return hip_fail(s, e, "craft_rollout_distances launch");
@@ -1316,13 +1274,10 @@ int craft_teacher(craft_sim_t* s, const int32_t* slots, int64_t n, const int32_t
   if (n == 0) return CRAFT_OK;
   if (!action_out || n < 0) return fail(s, CRAFT_EINVAL, "craft_teacher: bad argument");
   if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_teacher: n > n_envs");
-  if (4 * s->view.C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_teacher: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
-  if (n == 0) return CRAFT_OK;
-  {
-    const int frc = flush_table(s, stream, "craft_teacher");
-    if (frc != CRAFT_OK) return frc;
-  }
+  int rc = check_bfs_queue(s, "craft_teacher");
+  if (rc != CRAFT_OK) return rc;
+  rc = flush_table(s, stream, "craft_teacher");
+  if (rc != CRAFT_OK) return rc;
   hipError_t e = craft::launch_teacher(craft::teach_words(s->view.W, s->view.H), s->teach_lanes, teach_view(s), slots, tasks, n, action_out,
                                        path_len_out, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(s, e, "craft_teacher launch");
@@ -1335,7 +1290,6 @@ int craft_get_state(craft_sim_t* s, const int32_t* slots, int64_t n, int32_t* ag
   if (n == 0) return CRAFT_OK;
   if (n < 0) return fail(s, CRAFT_EINVAL, "craft_get_state: bad argument");
   if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_get_state: n > n_envs");
-  if (n == 0) return CRAFT_OK;
   hipLaunchKernelGGL(craft::get_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), s->view, slots, n, agent, inventory, grid, spec);
   hipError_t e = hipGetLastError();
@@ -1349,7 +1303,6 @@ int craft_set_state(craft_sim_t* s, const int32_t* slots, int64_t n, const int32
   if (n == 0) return CRAFT_OK;
   if (n < 0 || !spec || !agent) return fail(s, CRAFT_EINVAL, "craft_set_state: bad argument");
   if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_set_state: n > n_envs");
-  if (n == 0) return CRAFT_OK;
   hipLaunchKernelGGL(craft::set_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), s->view, slots, n, spec, agent, inventory);
   hipError_t e = hipGetLastError();

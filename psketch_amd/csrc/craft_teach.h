@@ -6,9 +6,28 @@
 // cleared-cell mask in HBM) and the fused tick + teacher kernel
 // (craft_tick_teach.hip: the post-step grid row already in LDS).
 #pragma once
+#include <type_traits>
+
 #include "craft_bits.h"
 
 namespace craft {
+
+// The kernels' NW template argument for nw = teach_words(W, H) words per BFS cell set, rounded up
+// to an instantiated one: 8x8 -> 2, 10x10 -> 3 (run as 4), 12x12 -> 4, 13x13 -> 5, 16x16 -> 7 (run
+// as 8).
+constexpr int teach_nw(int nw) { return nw <= 2 ? 2 : nw <= 4 ? 4 : nw <= 5 ? 5 : 8; }
+
+// teach_nw(nw) as a template argument: f(std::integral_constant<int, NW>).  Always inlined, so a
+// launcher built on it is the switch it would have written out (the tick launchers run every tick).
+template <class F>
+__attribute__((always_inline)) inline auto dispatch_nw(int nw, F f) {
+  switch (teach_nw(nw)) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
 
 // find_closest_resources (teachers/base.py:27-34) over shortest_path
 // (teachers/base.py:36-87), exactly, with one forward and one backward BFS over

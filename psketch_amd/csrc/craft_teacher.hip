@@ -4,6 +4,7 @@
 // teach_env (craft_teach.h).
 #include <cstdlib>
 
+#include "craft_launch.h"
 #include "craft_teach.h"
 
 namespace craft {
@@ -352,12 +353,9 @@ hipError_t launch_teach_table(int nw, const SimView& v, int32_t first, int32_t c
   const int64_t items = (int64_t)count * v.tt_nsub * v.tt_slots * 4 * v.C;
   const int64_t blocks = (LANES * items + 255) / 256;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-#define CRAFT_TT(NWV) hipLaunchKernelGGL((teach_table_kernel<NWV, LANES>), dim3((unsigned)blocks), dim3(256), 0, st, v, a)
-  if (nw <= 2) CRAFT_TT(2);
-  else if (nw <= 4) CRAFT_TT(4);
-  else if (nw <= 5) CRAFT_TT(5);
-  else CRAFT_TT(8);
-#undef CRAFT_TT
+  dispatch_nw(nw, [&](auto nwc) {
+    hipLaunchKernelGGL((teach_table_kernel<decltype(nwc)::value, LANES>), dim3((unsigned)blocks), dim3(256), 0, st, v, a);
+  });
   if (v.ttab4) {
     const int64_t bytes = (int64_t)count * v.tt_nsub * v.tt_slots * v.tt_blk;
     if ((bytes + 255) / 256 > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -372,46 +370,34 @@ hipError_t launch_distances(int nw, const SimView& v, const int32_t* tasks, cons
   DistArgs a{tasks, success, seqs, ticks, n, dist_out, is_get_out, n_actions_out, flags};
   const int lanes = n <= kTeacherQuadMaxItems ? 4 : 2;
   const unsigned blocks = (unsigned)((lanes * n + 255) / 256);
-#define CRAFT_DIST(NWV)                                                                                 \
-  do {                                                                                                  \
-    if (lanes == 4) hipLaunchKernelGGL((distances_kernel<NWV, 4>), dim3(blocks), dim3(256), 0, st, v, a); \
-    else hipLaunchKernelGGL((distances_kernel<NWV, 2>), dim3(blocks), dim3(256), 0, st, v, a);          \
-  } while (0)
-  if (nw <= 2) CRAFT_DIST(2);
-  else if (nw <= 4) CRAFT_DIST(4);
-  else if (nw <= 5) CRAFT_DIST(5);
-  else CRAFT_DIST(8);
-#undef CRAFT_DIST
+  dispatch_nw(nw, [&](auto nwc) {
+    constexpr int NW = decltype(nwc)::value;
+    if (lanes == 4) hipLaunchKernelGGL((distances_kernel<NW, 4>), dim3(blocks), dim3(256), 0, st, v, a);
+    else hipLaunchKernelGGL((distances_kernel<NW, 2>), dim3(blocks), dim3(256), 0, st, v, a);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_teacher(int nw, int forced, const SimView& v, const int32_t* slots, const int32_t* tasks,
                           int64_t n, int32_t* act_out, int32_t* len_out, hipStream_t st) {
   TeachArgs a{slots, tasks, n, act_out, len_out};
-  // nw = 32-bit words per BFS cell set (craft_teach.h: the band of columns 1 .. W-2):
-  // 8x8 -> 2, 10x10 -> 3 (run as 4), 12x12 -> 4, 16x16 -> 7 (run as 8)
+  // nw = 32-bit words per BFS cell set (craft_teach.h: the band of columns 1 .. W-2)
   // forced: craft_sim_tune_teach's lanes per query (1, 2 or 4), else 0: quads for small batches,
   // pairs above
   const int lanes = (forced == 1 || forced == 2 || forced == 4) ? forced : (n <= kTeacherQuadMaxItems ? 4 : 2);
   const unsigned blocks = (unsigned)((lanes * n + 255) / 256);
   // without path lengths the table's answers finish in the walk and the rest run densely
-#define CRAFT_TEACH_D(NWV, D)                                                                             \
-  do {                                                                                                    \
-    if (lanes == 4) hipLaunchKernelGGL((teacher_kernel<NWV, 4, D>), dim3(blocks), dim3(256), 0, st, v, a); \
-    else if (lanes == 2) hipLaunchKernelGGL((teacher_kernel<NWV, 2, D>), dim3(blocks), dim3(256), 0, st, v, a); \
-    else hipLaunchKernelGGL((teacher_kernel<NWV, 1, D>), dim3(blocks), dim3(256), 0, st, v, a);           \
-  } while (0)
-#define CRAFT_TEACH(NWV)                         \
-  do {                                           \
-    if (len_out) CRAFT_TEACH_D(NWV, false);      \
-    else CRAFT_TEACH_D(NWV, true);               \
-  } while (0)
-  if (nw <= 2) CRAFT_TEACH(2);
-  else if (nw <= 4) CRAFT_TEACH(4);
-  else if (nw <= 5) CRAFT_TEACH(5);
-  else CRAFT_TEACH(8);
-#undef CRAFT_TEACH
-#undef CRAFT_TEACH_D
+  dispatch_nw(nw, [&](auto nwc) {
+    constexpr int NW = decltype(nwc)::value;
+    auto with_dense = [&](auto dense) {
+      constexpr bool D = decltype(dense)::value;
+      if (lanes == 4) hipLaunchKernelGGL((teacher_kernel<NW, 4, D>), dim3(blocks), dim3(256), 0, st, v, a);
+      else if (lanes == 2) hipLaunchKernelGGL((teacher_kernel<NW, 2, D>), dim3(blocks), dim3(256), 0, st, v, a);
+      else hipLaunchKernelGGL((teacher_kernel<NW, 1, D>), dim3(blocks), dim3(256), 0, st, v, a);
+    };
+    if (len_out) with_dense(std::false_type{});
+    else with_dense(std::true_type{});
+  });
   return hipGetLastError();
 }
 

@@ -4,7 +4,8 @@
 // trainer's tick whose auto-reset moves a finished slot onto its next queue entry.  The launch
 // shapes are craft_tick_lang.hip's: with a label buffer the one-tile teacher shapes (the same
 // tiles, teacher lanes and cell-set words), without one the bare tick's.
-#include "craft_tile.h"
+#include "craft_launch.h"
+#include "craft_tile_launch.h"
 
 namespace craft {
 
@@ -59,72 +60,11 @@ hipError_t launch_queue_begin(const uint2* entries, int64_t count, int64_t first
   return hipGetLastError();
 }
 
-}  // namespace craft
-
-namespace craft {
-
-template <int WIN, int TILE>
-static hipError_t launch_sbare(const SimView& v, const TileArgs& a, size_t lds, hipStream_t st) {
-  const int64_t tiles = (a.n + TILE - 1) / TILE;
-  if (tiles == 0) return hipSuccess;
-  const hipError_t e = ensure_lds<&tile_kernel<WIN, MODE_STREAM, TILE>>(lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((tile_kernel<WIN, MODE_STREAM, TILE>), dim3((unsigned)tiles), dim3(kThreads), lds, st, v, a);
-  return hipGetLastError();
-}
-
-template <int TILE>
-static hipError_t launch_sbare_win(int win, const SimView& v, const TileArgs& a, size_t lds, hipStream_t st) {
-  switch (win) {
-    case 3: return launch_sbare<3, TILE>(v, a, lds, st);
-    case 5: return launch_sbare<5, TILE>(v, a, lds, st);
-    default: return launch_sbare<7, TILE>(v, a, lds, st);
-  }
-}
-
-template <int WIN, int TL, int NW, int TILE>
-static hipError_t launch_st(const SimView& v, const TileArgs& a, size_t lds, hipStream_t st) {
-  const int64_t tiles = (a.n + TILE - 1) / TILE;
-  if (tiles == 0) return hipSuccess;
-  const hipError_t e = ensure_lds<&tile_kernel<WIN, MODE_STREAM, TILE, TL, NW>>(lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((tile_kernel<WIN, MODE_STREAM, TILE, TL, NW>), dim3((unsigned)tiles),
-                     dim3(tile_tick_threads(TILE, TL) + TILE * TL), lds, st, v, a);
-  return hipGetLastError();
-}
-
-// 3x3 windows: 64-env tiles; wider ones 32 (the handle's default tile) or 64
-template <int TL, int NW>
-static hipError_t launch_st_win(int win, int tile, const SimView& v, const TileArgs& a, size_t lds, hipStream_t st) {
-  switch (win) {
-    case 3: return launch_st<3, TL, NW, kMaxTileEnvs>(v, a, lds, st);
-    case 5: return tile == 32 ? launch_st<5, TL, NW, 32>(v, a, lds, st) : launch_st<5, TL, NW, kMaxTileEnvs>(v, a, lds, st);
-    default: return tile == 32 ? launch_st<7, TL, NW, 32>(v, a, lds, st) : launch_st<7, TL, NW, kMaxTileEnvs>(v, a, lds, st);
-  }
-}
-
-template <int TL>
-static hipError_t launch_st_nw(int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds, hipStream_t st) {
-  // nw rounded up to an instantiated NW, as launch_tick_teach does
-  if (nw <= 2) return launch_st_win<TL, 2>(win, tile, v, a, lds, st);
-  if (nw <= 4) return launch_st_win<TL, 4>(win, tile, v, a, lds, st);
-  if (nw <= 5) return launch_st_win<TL, 5>(win, tile, v, a, lds, st);
-  return launch_st_win<TL, 8>(win, tile, v, a, lds, st);
-}
-
 // tl = teacher lanes per env (1, 2 or 4), or 0: no teacher in the launch (tile 16, 32 or 64).
 hipError_t launch_tick_stream(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                            hipStream_t st) {
-  if (tl == 0) {
-    switch (tile) {
-      case 16: return launch_sbare_win<16>(win, v, a, lds, st);
-      case 32: return launch_sbare_win<32>(win, v, a, lds, st);
-      default: return launch_sbare_win<64>(win, v, a, lds, st);
-    }
-  }
-  if (tl == 1) return launch_st_nw<1>(nw, win, tile, v, a, lds, st);
-  if (tl == 4) return launch_st_nw<4>(nw, win, tile, v, a, lds, st);
-  return launch_st_nw<2>(nw, win, tile, v, a, lds, st);
+                              hipStream_t st) {
+  if (tl == 0) return launch_tile_bare<MODE_STREAM>(win, tile, v, a, lds, st);
+  return launch_tile_teach<MODE_STREAM>(tl, nw, win, tile, v, a, lds, st);
 }
 
 }  // namespace craft

@@ -29,8 +29,8 @@ namespace craft {
 // episode-queue entry: the lanes that restart (and only they) fetch the entry, reload their grid
 // row from the new scenario's pool row and, with a teacher, the scenario's teacher words.
 //
-// TL > 0 (MODE_TICK and MODE_LANG only): TILE * TL more threads run the DemonstrationTeacher on
-// every env's new state (craft_step_teach), TL lanes per env, while the first
+// TL > 0 (MODE_TICK, MODE_LANG and MODE_STREAM only): TILE * TL more threads run the DemonstrationTeacher
+// on every env's new state (craft_step_teach), TL lanes per env, while the first
 // tick threads stream the observations: the BFS reads the grid rows the tick left in
 // LDS.  NW = 32-bit words per cell set (teach_env).
 #ifndef CRAFT_TT_WPE

@@ -19,6 +19,18 @@ def world_for(W, window):
     return name
 
 
+def row_ids(rows, n_base, added):
+    """ids= of parametrize rows (their first value the world) whose last len(added) values are
+    knobs added after the first n_base: pytest's own id of the first n_base values, then
+    "-<name><value>" for every knob a row sets (non-zero), so a row that sets none keeps the id it
+    had before the knobs existed."""
+    def one(i, v):
+        return v if isinstance(v, str) else str(v) if isinstance(v, (bool, int, float)) else f"world{i}"
+    return ["-".join(one(i, v) for v in row[:n_base]) +
+            "".join(f"-{name}{v}" for name, v in zip(added, row[n_base:]) if v)
+            for i, row in enumerate(rows)]
+
+
 def pad_inv(inv, K=32):
     inv = np.asarray(inv)
     out = np.zeros(inv.shape[:-1] + (K,), dtype=np.int32)

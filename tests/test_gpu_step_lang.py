@@ -9,7 +9,7 @@ import torch
 
 from psketch_amd import _native as N
 from psketch_amd import sample_scenarios, synthetic_specs
-from tests.helpers import make_tables
+from tests.helpers import make_tables, row_ids
 from tests.language_rollout_cases import (CASES, CASE_IDS, check_case, check_teacher_raise_of_ended_slot,
                                           make_sim)
 from tests.test_cpu_variant import cpu_sim
@@ -21,32 +21,48 @@ pytestmark = pytest.mark.gpu
 W12, W12_5 = "craft_medium_12x12", "craft_medium_12x12_w5"
 W15_7 = dict(WIDTH=15, HEIGHT=15, WINDOW_WIDTH=7, WINDOW_HEIGHT=7, N_WORKSHOPS=3, N_PRIMITIVES=2,
              N_WORLDS=100)
+W8 = "craft_medium"
+W13_5 = dict(WIDTH=13, HEIGHT=13, WINDOW_WIDTH=5, WINDOW_HEIGHT=5, N_WORKSHOPS=3, N_PRIMITIVES=2,
+             N_WORLDS=100)
 OUTPUTS = ("obs", "done", "success", "action_record", "ask_record", "transition_code", "labels")
 
 
 # n: 200 = three full 64-env tiles and one of 8 (3x3 windows); 72 = two 32-env tiles and 8 (5x5);
 # lanes / table: craft_sim_tune_teach's knobs (0 = default: quads on 64-env tiles, pairs on 32);
 # teach False: label_out NULL, the teacher-less launch
-@pytest.mark.parametrize("world,W,n,lanes,table,teach,fmt", [
-    (W12, 12, 200, 0, 0, True, "f32"),
-    (W12, 12, 200, 1, 2, True, "f32"),
-    (W12, 12, 200, 2, 0, True, "bf16"),
-    (W12, 12, 200, 4, 2, True, "u8"),
-    (W12, 12, 200, 0, 0, False, "f32"),
-    (W12_5, 12, 72, 1, 0, True, "f32"),
-    (W12_5, 12, 72, 2, 2, True, "f32"),
-    (W12_5, 12, 72, 4, 0, True, "bf16"),
-    (W12_5, 12, 72, 0, 0, False, "u8"),
-    (W15_7, 15, 40, 0, 0, True, "f32"),
-    (W15_7, 15, 40, 1, 2, True, "f32"),
-    (W15_7, 15, 40, 0, 0, False, "f32")])
-def test_step_lang_hip_equals_cpu_variant(world, W, n, lanes, table, teach, fmt):
+# tile: craft_sim_tune's tile_envs on the HIP side (0 = default: 64 at 3x3, 32 for wider windows)
+LANG_ROWS = [
+    (W12, 12, 200, 0, 0, True, "f32", 0),
+    (W12, 12, 200, 1, 2, True, "f32", 0),
+    (W12, 12, 200, 2, 0, True, "bf16", 0),
+    (W12, 12, 200, 4, 2, True, "u8", 0),
+    (W12, 12, 200, 0, 0, False, "f32", 0),
+    (W12_5, 12, 72, 1, 0, True, "f32", 0),
+    (W12_5, 12, 72, 2, 2, True, "f32", 0),
+    (W12_5, 12, 72, 4, 0, True, "bf16", 0),
+    (W12_5, 12, 72, 0, 0, False, "u8", 0),
+    (W15_7, 15, 40, 0, 0, True, "f32", 0),
+    (W15_7, 15, 40, 1, 2, True, "f32", 0),
+    (W15_7, 15, 40, 0, 0, False, "f32", 0),
+    (W8, 8, 70, 0, 0, True, "f32", 0),            # 8x8: 2 words per cell set; a 64-env tile and one of 6
+    (W13_5, 13, 40, 0, 0, True, "f32", 0),        # 13x13: 5 words; a 32-env tile and one of 8
+    (W12_5, 12, 72, 0, 0, True, "f32", 64),       # the 64-env teacher tile on a wide window: quads,
+    (W12_5, 12, 72, 2, 0, True, "f32", 64),       # pairs
+    (W12, 12, 72, 0, 0, False, "f32", 16),        # the bare tick on 16- and 64-env tiles
+    (W12_5, 12, 72, 0, 0, False, "f32", 16),
+    (W12_5, 12, 72, 0, 0, False, "f32", 64)]
+
+
+@pytest.mark.parametrize("world,W,n,lanes,table,teach,fmt,tile", LANG_ROWS, ids=row_ids(LANG_ROWS, 7, ("tile",)))
+def test_step_lang_hip_equals_cpu_variant(world, W, n, lanes, table, teach, fmt, tile):
     T, ticks = 12, 14
     params, cb, tm, cfg = make_tables(world, T)
     pool, _, _ = sample_scenarios(params, cb, 123, 24)
     specs = synthetic_specs(pool, W, W, n, 0, seed=6, task_ids=[t.id for t in tm.dataset_tasks()])
     g, c = sim_with_pool(world, n, pool, max_timesteps=T), cpu_sim(world, n, pool, max_timesteps=T)
     g.tune_teach(1, lanes, table)
+    if tile:
+        g.tune(tile_envs=tile, obs_store=2)      # (2: the store policy of an untuned handle)
     for s in (g, c):
         s.set_obs_format(fmt)
         s.reset(*specs)

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from tests.evaluate_cases import check_evaluate_equals_do_rollout, check_evaluate_equals_reference
+from tests.helpers import row_ids
 from tests.stream_cases import (STREAM_OUTPUTS, T_MAX, check_against_composition, queue_inputs, run_lockstep,
                                 stream_buffers)
 from tests.test_cpu_variant import cpu_sim
@@ -17,28 +18,44 @@ pytestmark = pytest.mark.gpu
 W12, W12_5 = "craft_medium_12x12", "craft_medium_12x12_w5"
 W15_7 = dict(WIDTH=15, HEIGHT=15, WINDOW_WIDTH=7, WINDOW_HEIGHT=7, N_WORKSHOPS=3, N_PRIMITIVES=2,
              N_WORLDS=100)
+W8 = "craft_medium"
+W13_5 = dict(WIDTH=13, HEIGHT=13, WINDOW_WIDTH=5, WINDOW_HEIGHT=5, N_WORKSHOPS=3, N_PRIMITIVES=2,
+             N_WORLDS=100)
 
 
 # n: 200 = three full 64-env tiles and one of 8 (3x3 windows); 72 = two 32-env tiles and 8 (5x5);
 # lanes / table: craft_sim_tune_teach's knobs (0 = default: quads on 64-env tiles, pairs on 32);
 # teach False: label_out NULL, the teacher-less launch
+# tile: craft_sim_tune's tile_envs on the HIP side (0 = default: 64 at 3x3, 32 for wider windows)
+STREAM_ROWS = [
+    (W12, 12, 200, 0, 0, True, "f32", 0),
+    (W12, 12, 200, 1, 2, True, "bf16", 0),
+    (W12, 12, 200, 2, 0, True, "u8", 0),
+    (W12, 12, 200, 4, 2, True, "f32", 0),
+    (W12, 12, 200, 0, 0, False, "f32", 0),
+    (W12_5, 12, 72, 1, 0, True, "f32", 0),
+    (W12_5, 12, 72, 2, 2, True, "bf16", 0),
+    (W12_5, 12, 72, 4, 0, True, "f32", 0),
+    (W12_5, 12, 72, 0, 0, False, "u8", 0),
+    (W15_7, 15, 40, 0, 0, True, "f32", 0),
+    (W15_7, 15, 40, 0, 0, False, "f32", 0),
+    (W8, 8, 70, 0, 0, True, "f32", 0),            # 8x8: 2 words per cell set; a 64-env tile and one of 6
+    (W13_5, 13, 40, 0, 0, True, "f32", 0),        # 13x13: 5 words; a 32-env tile and one of 8
+    (W12_5, 12, 72, 0, 0, True, "f32", 64),       # the 64-env teacher tile on a wide window: quads,
+    (W12_5, 12, 72, 2, 0, True, "f32", 64),       # pairs
+    (W12, 12, 72, 0, 0, False, "f32", 16),        # the bare tick on 16- and 64-env tiles
+    (W12_5, 12, 72, 0, 0, False, "f32", 16),
+    (W12_5, 12, 72, 0, 0, False, "f32", 64)]
+
+
 @pytest.mark.parametrize("wrap", [False, True], ids=["one_pass", "wrap"])
-@pytest.mark.parametrize("world,W,n,lanes,table,teach,fmt", [
-    (W12, 12, 200, 0, 0, True, "f32"),
-    (W12, 12, 200, 1, 2, True, "bf16"),
-    (W12, 12, 200, 2, 0, True, "u8"),
-    (W12, 12, 200, 4, 2, True, "f32"),
-    (W12, 12, 200, 0, 0, False, "f32"),
-    (W12_5, 12, 72, 1, 0, True, "f32"),
-    (W12_5, 12, 72, 2, 2, True, "bf16"),
-    (W12_5, 12, 72, 4, 0, True, "f32"),
-    (W12_5, 12, 72, 0, 0, False, "u8"),
-    (W15_7, 15, 40, 0, 0, True, "f32"),
-    (W15_7, 15, 40, 0, 0, False, "f32")])
-def test_step_stream_hip_equals_cpu_variant(world, W, n, lanes, table, teach, fmt, wrap):
+@pytest.mark.parametrize("world,W,n,lanes,table,teach,fmt,tile", STREAM_ROWS, ids=row_ids(STREAM_ROWS, 7, ("tile",)))
+def test_step_stream_hip_equals_cpu_variant(world, W, n, lanes, table, teach, fmt, tile, wrap):
     pool, specs = queue_inputs(world, W, n)
     g, c = sim_with_pool(world, n, pool, max_timesteps=T_MAX), cpu_sim(world, n, pool, max_timesteps=T_MAX)
     g.tune_teach(1, lanes, table)
+    if tile:
+        g.tune(tile_envs=tile, obs_store=2)      # (2: the store policy of an untuned handle)
     for s in (g, c):
         s.set_obs_format(fmt)
     run_lockstep(g, c, specs, wrap, teach=teach)

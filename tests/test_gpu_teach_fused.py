@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from psketch_amd import sample_scenarios, synthetic_specs
-from tests.helpers import make_tables
+from tests.helpers import make_tables, row_ids
 from tests.test_gpu_parity import host, sim_with_pool
 
 pytestmark = pytest.mark.gpu
@@ -65,20 +65,31 @@ def test_step_teach_equals_step_then_teacher(world, W, n, T, autoreset, given, k
 # threads beside the teacher pairs, each env's teacher word and the deferred BFS list in row
 # padding, task_sub as bytes (craft_tile.h).  table 2: every go leaf is a deferred BFS, so the
 # list fills; USE raised in the given actions, so cells are cleared and recipes run.
-@pytest.mark.parametrize("world,W,n,T,table,given", [
-    ("craft_medium_12x12_w5", 12, 65536, 10, 0, False),   # config 5's size: four workgroups per CU
-    ("craft_medium_12x12_w5", 12, 5000, 30, 2, True),     # the deferred list full; a partial tile
-    ("craft_large", 10, 4000, 25, 2, True),
+# tile / lanes: craft_sim_tune's tile_envs and craft_sim_tune_teach's lanes (0 = default: the 32-env
+# tile with pairs; tile_envs 64: the 64-env tile, quads unless lanes says pairs).
+WIDE_ROWS = [
+    ("craft_medium_12x12_w5", 12, 65536, 10, 0, False, 0, 0),   # config 5's size: four workgroups per CU
+    ("craft_medium_12x12_w5", 12, 5000, 30, 2, True, 0, 0),     # the deferred list full; a partial tile
+    ("craft_large", 10, 4000, 25, 2, True, 0, 0),
     (dict(WIDTH=12, HEIGHT=12, WINDOW_WIDTH=7, WINDOW_HEIGHT=7, N_WORKSHOPS=3, N_PRIMITIVES=2, N_WORLDS=100),
-     12, 3000, 25, 2, True)])
-def test_step_teach_wide_windows_equal_step_then_teacher(world, W, n, T, table, given):
+     12, 3000, 25, 2, True, 0, 0),
+    (dict(WIDTH=13, HEIGHT=13, WINDOW_WIDTH=5, WINDOW_HEIGHT=5, N_WORKSHOPS=3, N_PRIMITIVES=2, N_WORLDS=100),
+     13, 40, 14, 0, True, 0, 0),                                # 13x13: five words per cell set
+    ("craft_medium_12x12_w5", 12, 72, 14, 0, True, 64, 0),      # the 64-env tile (and one of 8): quads,
+    ("craft_medium_12x12_w5", 12, 72, 14, 0, True, 64, 2)]      # pairs
+
+
+@pytest.mark.parametrize("world,W,n,T,table,given,tile,lanes", WIDE_ROWS, ids=row_ids(WIDE_ROWS, 6, ("tile", "lanes")))
+def test_step_teach_wide_windows_equal_step_then_teacher(world, W, n, T, table, given, tile, lanes):
     params, cb, tm, cfg = make_tables(world)
     pool, _, _ = sample_scenarios(params, cb, 123, 256)
     specs = synthetic_specs(pool, W, W, n, 0, seed=11, task_ids=[t.id for t in tm.dataset_tasks()])
     a, b = sim_with_pool(world, n, pool), sim_with_pool(world, n, pool)
-    a.tune_teach(1, 0, table)
-    kname, envs, lanes = a.step_shape(teach=True)
-    assert (envs, lanes) == (32, 2), (kname, envs, lanes)
+    a.tune_teach(1, lanes, table)
+    if tile:
+        a.tune(tile_envs=tile, obs_store=2)               # (2: the store policy of an untuned handle)
+    kname, envs, tl = a.step_shape(teach=True)
+    assert (envs, tl) == ((64, lanes or 4) if tile == 64 else (32, 2)), (kname, envs, tl)
     a.reset(*specs)
     b.reset(*specs)
     F = a.n_features
