@@ -112,7 +112,9 @@ typedef struct craft_task {
  * (worlds/cookbook.py:8-26), TaskManager (data/task.py:32-75). */
 typedef struct craft_config {
   int32_t abi_version;       /* = CRAFT_ABI_VERSION */
-  int32_t width, height;     /* WIDTH, HEIGHT */
+  int32_t width, height;     /* WIDTH, HEIGHT: independent (3..16 each, width*height <= 256; cells are
+                              * x*height + y).  The teacher entry points refuse 4*W*H > 1000, so
+                              * 15x16 and 16x15 are the largest worlds they label. */
   int32_t window_width, window_height;   /* WINDOW_WIDTH, WINDOW_HEIGHT (odd, equal, 3..7) */
   int32_t n_kinds;           /* len(cookbook.index) */
   int32_t n_features;        /* must equal 2*ww*wh*n_kinds + n_kinds + 5 (craft.py:69-75) */
@@ -172,7 +174,9 @@ int craft_sim_tune(craft_sim_t* sim, int32_t tile_envs, int32_t max_resident_per
  * tiles also take 512.  16- and 32-env tiles with 320, 384 or 512: the
  * split-producer kernel (transition and scatter on two waves, the other 3-6
  * stream).  0 (default) = the measured best: 32-env tiles x 512 threads (split)
- * for 3x3 windows, else the handle's tile with 256 threads (512 for 64-env tiles). */
+ * for 3x3 windows, else the handle's tile with 256 threads (512 for 64-env tiles).  A tile whose
+ * two staged observation buffers do not fit a workgroup's 160 KiB of LDS (64 envs at 7x7 windows)
+ * runs as the largest tile that does; craft_sim_rollout_shape reports it. */
 int craft_sim_tune_rollout(craft_sim_t* sim, int32_t chunk_ticks, int32_t threads);
 
 /* The teacher's knobs (results are identical for every setting; a tuning knob like

@@ -233,6 +233,9 @@ void rollout_shape(const craft_sim* s, int* tile, int* threads, int* split) {
     t = 32;
     nt = 512;
   }
+  // a tile whose two staged observation buffers exceed a workgroup's 160 KiB of LDS (64 envs at
+  // 7x7 windows: 300 KB; at 5x5 from 16x16 worlds) cannot launch: it runs as the largest that fits
+  while (t > 16 && lds_bytes(s, t, 2, true) > 163840) t /= 2;
   // what launch_rollout_win (craft_rollout.h) instantiates for (t, nt): 64-env tiles run 256
   // or 512 threads, smaller tiles 128, the split kernel at 320 / 384 / 512, else 256
   if (t == 64) nt = (nt == 256) ? 256 : 512;

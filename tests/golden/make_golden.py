@@ -2,6 +2,7 @@
 
 Run in the build container only (needs /root/reference, read-only):
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py rect      # only rect_worlds.npz: worlds with WIDTH != HEIGHT
 
 What it imports from the reference: worlds (CraftWorld/CraftState/Cookbook),
 data.task (TaskManager), teachers (DemonstrationTeacher), misc.util, and the
@@ -75,11 +76,13 @@ def make_config(world_yaml="craft_medium", seed=123):
     return cfg
 
 
-def make_world(W=None, window=None, seed=123):
+def make_world(W=None, window=None, seed=123, H=None, prims=None):
     cfg = make_config(seed=seed)
     world = worlds.load(cfg)
     if W is not None:
-        world.WIDTH = world.HEIGHT = W
+        world.WIDTH, world.HEIGHT = W, (W if H is None else H)
+    if prims is not None:
+        world.N_PRIMITIVES = prims
     if window is not None:
         world.WINDOW_WIDTH = world.WINDOW_HEIGHT = window
         world.n_features = 2 * window * window * world.cookbook.n_kinds + world.cookbook.n_kinds + 5
@@ -192,34 +195,38 @@ def gen_scenarios():
     first 64 worlds at 12x12."""
     arrays = {}
     for name, W, count in [("w8", 8, 100), ("w12", 12, 64)]:
-        cfg, world = make_world(W)
-        fns = make_data_functions(world)
-        ingredients = [world.cookbook.index[i] for i in ["wood", "grass", "iron"]]
-        grids, inits = [], []
-        while len(grids) < count:
-            grid, init_pos = fns["sample_scenario"](world, ingredients, cfg)
-            if any((grid == g).all() for g in grids):
-                continue
-            grids.append(grid)
-            inits.append(init_pos)
-        arrays[f"{name}_grids"] = np.stack([onehot_to_ids(g).reshape(-1) for g in grids])
-        arrays[f"{name}_init"] = np.asarray(inits, dtype=np.int32)
-        st = cfg.random.get_state()
-        arrays[f"{name}_mt_key"] = np.asarray(st[1], dtype=np.uint32)
-        arrays[f"{name}_mt_pos"] = np.asarray([st[2]], dtype=np.int32)
+        scenario_arrays(arrays, name, W, W, count)
         print("scenarios", name, arrays[f"{name}_grids"].shape)
     np.savez_compressed(os.path.join(OUT, "scenarios_seed123.npz"), **arrays)
     return arrays
 
 
-def gen_rollout(w12_grids, window, T, E, P, all_obs_ticks):
+def scenario_arrays(arrays, name, W, H, count, prims=None):
+    """The first `count` de-duplicated sample_scenario worlds from RandomState(123)."""
+    cfg, world = make_world(W, H=H, prims=prims)
+    fns = make_data_functions(world)
+    ingredients = [world.cookbook.index[i] for i in ["wood", "grass", "iron"]]
+    grids, inits = [], []
+    while len(grids) < count:
+        grid, init_pos = fns["sample_scenario"](world, ingredients, cfg)
+        if any((grid == g).all() for g in grids):
+            continue
+        grids.append(grid)
+        inits.append(init_pos)
+    arrays[f"{name}_grids"] = np.stack([onehot_to_ids(g).reshape(-1) for g in grids])
+    arrays[f"{name}_init"] = np.asarray(inits, dtype=np.int32)
+    st = cfg.random.get_state()
+    arrays[f"{name}_mt_key"] = np.asarray(st[1], dtype=np.uint32)
+    arrays[f"{name}_mt_pos"] = np.asarray([st[2]], dtype=np.int32)
+
+
+def gen_rollout(w12_grids, window, T, E, P, all_obs_ticks, W=12, H=12, prims=None, save=True):
     """Synthetic random-action rollouts through the reference's CraftState,
     with ImitationTrainer.do_rollout's per-env protocol (imitation.py:59-73)
     and auto-reset to the env's initial state."""
-    cfg, world = make_world(12, window)
+    cfg, world = make_world(W, window, H=H, prims=prims)
     tm = TaskManager(cfg)
     K = world.cookbook.n_kinds
-    W = H = 12
     task_objs = list(tm.tasks)
     task_list = [i for i, t in enumerate(task_objs) if t.goal_name in ("get", "make")]
     pool = w12_grids[:P]
@@ -286,26 +293,32 @@ def gen_rollout(w12_grids, window, T, E, P, all_obs_ticks):
     arrays["pool"] = pool
     arrays["spec"] = np.stack([scen, xs, ys, dirs, tasks], axis=1).astype(np.int32)
     arrays["seed"] = np.asarray([seed])
+    if not save:
+        return arrays
     name = f"rollout_12x12_w{window}.npz"
     np.savez_compressed(os.path.join(OUT, name), **arrays)
     print(name, os.path.getsize(os.path.join(OUT, name)))
 
 
-def random_state_cases(n, W, seed):
+def random_state_cases(n, W, seed, H=None, window=None, prims=None):
     """Random grids with the boundary ring and arbitrary interior kinds."""
-    cfg, world = make_world(W)
+    H = W if H is None else H
+    cfg, world = make_world(W, window, H=H, prims=prims)
     tm = TaskManager(cfg)
     K = world.cookbook.n_kinds
     rng = np.random.RandomState(seed)
     cases = []
     for i in range(n):
-        g = np.zeros((W, W), dtype=np.int64)
+        g = np.zeros((W, H), dtype=np.int64)
         g[0, :] = g[-1, :] = g[:, 0] = g[:, -1] = 1
         dens = rng.uniform(0.1, 0.6)
-        inner = rng.randint(1, K, size=(W - 2, W - 2))
+        inner = rng.randint(1, K, size=(W - 2, H - 2))
         inner[rng.uniform(size=inner.shape) > dens] = 0
         g[1:-1, 1:-1] = inner
-        x, y = rng.randint(1, W - 1, size=2)
+        if H == W:
+            x, y = rng.randint(1, W - 1, size=2)
+        else:
+            x, y = rng.randint(1, W - 1), rng.randint(1, H - 1)
         if rng.uniform() < 0.9:
             g[x, y] = 0
         d = rng.randint(4)
@@ -321,41 +334,44 @@ def random_state_cases(n, W, seed):
 def gen_kat_step():
     arrays = {}
     for W in (8, 12):
-        cfg, world, tm, cases = random_state_cases(1500, W, 1000 + W)
-        K = world.cookbook.n_kinds
-        pre_grid, pre_agent, pre_inv, act = [], [], [], []
-        post_grid, post_agent, post_inv, feats, sats = [], [], [], [], []
-        for g, x, y, d, inv, a in cases:
-            st = world.init_state(ids_to_onehot(g, K), (int(x), int(y)), int(d))
-            st.inventory = inv.astype(np.float64)
-            f = st.features().astype(np.uint8)
-            s_all = []
-            for t in tm.tasks:
-                try:
-                    s = st.satisfies(t)
-                    s_all.append(-1 if s is None else int(bool(s)))
-                except Exception:
-                    s_all.append(-9)
-            _, st2 = st.step(int(a))
-            pre_grid.append(g.reshape(-1)); pre_agent.append([x, y, d]); pre_inv.append(inv)
-            act.append(a)
-            post_grid.append(onehot_to_ids(st2.grid).reshape(-1))
-            post_agent.append([st2.pos[0], st2.pos[1], st2.dir])
-            post_inv.append(np.asarray(st2.inventory, dtype=np.int64))
-            feats.append(f)
-            sats.append(s_all)
-        p = f"w{W}_"
-        arrays[p + "pre_grid"] = np.asarray(pre_grid, dtype=np.uint8)
-        arrays[p + "pre_agent"] = np.asarray(pre_agent, dtype=np.int8)
-        arrays[p + "pre_inv"] = np.asarray(pre_inv, dtype=np.uint8)
-        arrays[p + "action"] = np.asarray(act, dtype=np.int8)
-        arrays[p + "post_grid"] = np.asarray(post_grid, dtype=np.uint8)
-        arrays[p + "post_agent"] = np.asarray(post_agent, dtype=np.int8)
-        arrays[p + "post_inv"] = np.asarray(post_inv, dtype=np.uint8)
-        arrays[p + "features"] = np.asarray(feats, dtype=np.uint8)
-        arrays[p + "satisfies"] = np.asarray(sats, dtype=np.int8)
+        kat_step_arrays(arrays, f"w{W}_", *random_state_cases(1500, W, 1000 + W))
     np.savez_compressed(os.path.join(OUT, "kat_step.npz"), **arrays)
     print("kat_step.npz", os.path.getsize(os.path.join(OUT, "kat_step.npz")))
+
+
+def kat_step_arrays(arrays, p, cfg, world, tm, cases):
+    """features / satisfies / step of every case, into arrays[p + ...]."""
+    K = world.cookbook.n_kinds
+    pre_grid, pre_agent, pre_inv, act = [], [], [], []
+    post_grid, post_agent, post_inv, feats, sats = [], [], [], [], []
+    for g, x, y, d, inv, a in cases:
+        st = world.init_state(ids_to_onehot(g, K), (int(x), int(y)), int(d))
+        st.inventory = inv.astype(np.float64)
+        f = st.features().astype(np.uint8)
+        s_all = []
+        for t in tm.tasks:
+            try:
+                s = st.satisfies(t)
+                s_all.append(-1 if s is None else int(bool(s)))
+            except Exception:
+                s_all.append(-9)
+        _, st2 = st.step(int(a))
+        pre_grid.append(g.reshape(-1)); pre_agent.append([x, y, d]); pre_inv.append(inv)
+        act.append(a)
+        post_grid.append(onehot_to_ids(st2.grid).reshape(-1))
+        post_agent.append([st2.pos[0], st2.pos[1], st2.dir])
+        post_inv.append(np.asarray(st2.inventory, dtype=np.int64))
+        feats.append(f)
+        sats.append(s_all)
+    arrays[p + "pre_grid"] = np.asarray(pre_grid, dtype=np.uint8)
+    arrays[p + "pre_agent"] = np.asarray(pre_agent, dtype=np.int8)
+    arrays[p + "pre_inv"] = np.asarray(pre_inv, dtype=np.uint8)
+    arrays[p + "action"] = np.asarray(act, dtype=np.int8)
+    arrays[p + "post_grid"] = np.asarray(post_grid, dtype=np.uint8)
+    arrays[p + "post_agent"] = np.asarray(post_agent, dtype=np.int8)
+    arrays[p + "post_inv"] = np.asarray(post_inv, dtype=np.uint8)
+    arrays[p + "features"] = np.asarray(feats, dtype=np.uint8)
+    arrays[p + "satisfies"] = np.asarray(sats, dtype=np.int8)
 
 
 def gen_kat_edges():
@@ -411,10 +427,10 @@ def gen_kat_edges():
     print("kat_edges.json", len(cases))
 
 
-def gen_teacher(w12_grids, n_states=400):
+def gen_teacher(w12_grids, n_states=400, W=12, H=12, window=None, prims=None, save=True):
     """DemonstrationTeacher actions and find_closest_resources lengths on 12x12
     worlds, random positions/directions/inventories, every task."""
-    cfg, world = make_world(12)
+    cfg, world = make_world(W, window, H=H, prims=prims)
     tm = TaskManager(cfg)
     teacher = teachers.load(cfg)
     K = world.cookbook.n_kinds
@@ -423,14 +439,14 @@ def gen_teacher(w12_grids, n_states=400):
     items = ["wood", "grass", "iron", "plank", "stick", "axe", "rope", "bridge"]
     grids, agents, invs, acts, lens = [], [], [], [], []
     for i in range(n_states):
-        g = w12_grids[rng.randint(len(w12_grids))].reshape(12, 12).astype(np.int64).copy()
+        g = w12_grids[rng.randint(len(w12_grids))].reshape(W, H).astype(np.int64).copy()
         # sometimes remove a resource (as grabbing does) to vary the targets
         for _ in range(rng.randint(0, 3)):
-            cells = [(x, y) for x in range(12) for y in range(12) if g[x, y] in (7, 8, 9)]
+            cells = [(x, y) for x in range(W) for y in range(H) if g[x, y] in (7, 8, 9)]
             if cells:
                 x, y = cells[rng.randint(len(cells))]
                 g[x, y] = 0
-        free = [(x, y) for x in range(1, 11) for y in range(1, 11) if g[x, y] == 0]
+        free = [(x, y) for x in range(1, W - 1) for y in range(1, H - 1) if g[x, y] == 0]
         x, y = free[rng.randint(len(free))]
         d = rng.randint(4)
         inv = np.zeros(K)
@@ -455,10 +471,12 @@ def gen_teacher(w12_grids, n_states=400):
                 row_l.append(-3)
         grids.append(g.reshape(-1)); agents.append([x, y, d]); invs.append(inv)
         acts.append(row_a); lens.append(row_l)
-    np.savez_compressed(os.path.join(OUT, "teacher_12x12.npz"),
-                        grid=np.asarray(grids, dtype=np.uint8), agent=np.asarray(agents, dtype=np.int8),
-                        inv=np.asarray(invs, dtype=np.uint8), action=np.asarray(acts, dtype=np.int8),
-                        path_len=np.asarray(lens, dtype=np.int16))
+    arrays = dict(grid=np.asarray(grids, dtype=np.uint8), agent=np.asarray(agents, dtype=np.int8),
+                  inv=np.asarray(invs, dtype=np.uint8), action=np.asarray(acts, dtype=np.int8),
+                  path_len=np.asarray(lens, dtype=np.int16))
+    if not save:
+        return arrays
+    np.savez_compressed(os.path.join(OUT, "teacher_12x12.npz"), **arrays)
     print("teacher_12x12.npz", np.unique(np.asarray(acts), return_counts=True))
 
 
@@ -728,7 +746,35 @@ def gen_config1(T=100, seed=1):
     print("config1_train0.npz", task_id, pos, len(demo), os.path.getsize(os.path.join(OUT, "config1_train0.npz")))
 
 
+RECT = [("r7x13", 7, 13, 3, 2), ("r13x7", 13, 7, 5, 2), ("r5x16", 5, 16, 7, 1), ("r15x16", 15, 16, 7, 2)]
+
+
+def gen_rect(n_kat=180, n_scen=24, n_teacher=120, E=24, T=50):
+    """rect_worlds.npz: worlds with WIDTH != HEIGHT (tag, W, H, window, N_PRIMITIVES in RECT), each
+    with the layouts of the square fixtures under a "<tag>_<fixture>_" prefix: kat_ (kat_step.npz),
+    scen_ (scenarios_seed123.npz), teacher_ (teacher_12x12.npz, states on the scen_ worlds) and
+    rollout_ (rollout_12x12_w*.npz, 16 scen_ worlds, observations of every tick).  The counts keep
+    the file under the size of kat_step.npz, the largest fixture."""
+    arrays = {}
+    for tag, W, H, window, prims in RECT:
+        kat_step_arrays(arrays, f"{tag}_kat_", *random_state_cases(n_kat, W, 1000 + 16 * W + H, H=H,
+                                                                   window=window, prims=prims))
+        scenario_arrays(arrays, f"{tag}_scen", W, H, n_scen, prims=prims)
+        grids = arrays[f"{tag}_scen_grids"]
+        for k, v in gen_teacher(grids, n_teacher, W, H, window, prims, save=False).items():
+            arrays[f"{tag}_teacher_{k}"] = v
+        for k, v in gen_rollout(grids, window, T, E, 16, None, W, H, prims, save=False).items():
+            arrays[f"{tag}_rollout_{k}"] = v
+        print(tag, "teacher actions", np.unique(arrays[f"{tag}_teacher_action"], return_counts=True))
+    path = os.path.join(OUT, "rect_worlds.npz")
+    np.savez_compressed(path, **arrays)
+    print("rect_worlds.npz", os.path.getsize(path))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["rect"]:                # only the WIDTH != HEIGHT fixture
+        gen_rect()
+        sys.exit(0)
     if sys.argv[1:] == ["language"]:            # only the language-teacher fixture
         gen_language(np.load(os.path.join(OUT, "scenarios_seed123.npz"))["w12_grids"])
         sys.exit(0)

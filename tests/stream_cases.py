@@ -15,14 +15,14 @@ STREAM_OUTPUTS = ("obs", "reward", "done", "success", "action_record", "transiti
                   "episode_end", "end_pose", "episode_now")
 
 
-def queue_inputs(world, W, n, seed=11, pool_size=24):
+def queue_inputs(world, W, n, seed=11, pool_size=24, H=None):
     """A pool of `pool_size` scenarios and a queue of 3n + 17 episode specs over it (not a
     multiple of n: slots run out on different ticks), in shuffled order so that a slot's
     consecutive entries differ in scenario and task whatever n is, with every start direction."""
     params, cb, tm, cfg = make_tables(world, T_MAX)
     pool, _, _ = sample_scenarios(params, cb, 123, pool_size)
     count = 3 * n + 17
-    specs = np.stack(synthetic_specs(pool, W, W, count, 0, seed=seed,
+    specs = np.stack(synthetic_specs(pool, W, W if H is None else H, count, 0, seed=seed,
                                      task_ids=[t.id for t in tm.dataset_tasks()]), 1).astype(np.int32)
     rng = np.random.RandomState(seed)
     specs = specs[rng.permutation(count)]

@@ -55,10 +55,15 @@ LANG_ROWS = [
 
 @pytest.mark.parametrize("world,W,n,lanes,table,teach,fmt,tile", LANG_ROWS, ids=row_ids(LANG_ROWS, 7, ("tile",)))
 def test_step_lang_hip_equals_cpu_variant(world, W, n, lanes, table, teach, fmt, tile):
+    lang_lockstep(world, W, n, lanes, table, teach, fmt, tile)
+
+
+def lang_lockstep(world, W, n, lanes, table, teach, fmt, tile, H=None):
+    """One LANG_ROWS row (H: the world's height where it is not W)."""
     T, ticks = 12, 14
     params, cb, tm, cfg = make_tables(world, T)
     pool, _, _ = sample_scenarios(params, cb, 123, 24)
-    specs = synthetic_specs(pool, W, W, n, 0, seed=6, task_ids=[t.id for t in tm.dataset_tasks()])
+    specs = synthetic_specs(pool, W, W if H is None else H, n, 0, seed=6, task_ids=[t.id for t in tm.dataset_tasks()])
     g, c = sim_with_pool(world, n, pool, max_timesteps=T), cpu_sim(world, n, pool, max_timesteps=T)
     g.tune_teach(1, lanes, table)
     if tile:

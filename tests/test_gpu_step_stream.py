@@ -51,7 +51,12 @@ STREAM_ROWS = [
 @pytest.mark.parametrize("wrap", [False, True], ids=["one_pass", "wrap"])
 @pytest.mark.parametrize("world,W,n,lanes,table,teach,fmt,tile", STREAM_ROWS, ids=row_ids(STREAM_ROWS, 7, ("tile",)))
 def test_step_stream_hip_equals_cpu_variant(world, W, n, lanes, table, teach, fmt, tile, wrap):
-    pool, specs = queue_inputs(world, W, n)
+    stream_lockstep(world, W, n, lanes, table, teach, fmt, tile, wrap)
+
+
+def stream_lockstep(world, W, n, lanes, table, teach, fmt, tile, wrap, H=None):
+    """One STREAM_ROWS row (H: the world's height where it is not W)."""
+    pool, specs = queue_inputs(world, W, n, H=H)
     g, c = sim_with_pool(world, n, pool, max_timesteps=T_MAX), cpu_sim(world, n, pool, max_timesteps=T_MAX)
     g.tune_teach(1, lanes, table)
     if tile:
