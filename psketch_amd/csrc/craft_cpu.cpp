@@ -7,8 +7,9 @@
 //
 // The state layout is the HIP library's (include/craft.h, craft_device.h): per slot a packed u64
 // state word, the restart word, 32 u8 inventory counts and a 256-bit cleared-cell mask over the
-// scenario's pool row; configuration, pool and task-table checks come from craft_host.h, so
-// both libraries accept and refuse the same inputs.  Work is split over host threads by
+// scenario's pool row; configuration, pool, task-table and every entry point's argument checks,
+// and the validated tuning knobs, come from craft_host.h / craft_checks.h, so both libraries
+// accept and refuse the same inputs.  Work is split over host threads by
 // contiguous slot ranges (craft_sim_tune_host; default: the hardware's threads).  Results equal the HIP
 // library's bit for bit (tests/test_cpu_variant.py against the oracle here, tests/test_gpu_cpu_variant.py
 // against the HIP library on the GPU box).
@@ -102,8 +103,6 @@ uint64_t pack_state(const Agent& a) {
 inline int dir_dx(int d) { return d == CRAFT_LEFT ? -1 : (d == CRAFT_RIGHT ? 1 : 0); }
 inline int dir_dy(int d) { return d == CRAFT_DOWN ? -1 : (d == CRAFT_UP ? 1 : 0); }
 
-int default_tile(int win) { return win == 3 ? 64 : 32; }     // as the HIP library's (u8 rows)
-
 }  // namespace
 
 struct craft_sim {
@@ -121,9 +120,7 @@ struct craft_sim {
   std::atomic<int64_t> stats[3];
   std::atomic<int32_t> err_code{0};
   std::atomic<int64_t> err_slot{-1};
-  int obs_fmt = CRAFT_OBS_F32;
-  int tile = 64, obs_store = 2, resident_cap = 0, rollout_chunk = 0, rollout_threads = 0, teach_kernel = 0;
-  int teach_lanes = 0, teach_table = 0;
+  craft_host::Knobs k;                    // validated and reported back; only obs_fmt changes anything here
   int threads = 1;
   // the episode queue: the specs as given (checked at install), each slot's index (-1: run out)
   struct QueueEntry { int32_t scen, x, y, dir, task; };
@@ -139,6 +136,12 @@ namespace {
 int fail(craft_sim* s, int code, const std::string& msg) {
   if (s) s->last_error = msg;
   return code;
+}
+
+// What the shared argument checks (craft_checks.h) read of the handle.
+craft_host::Facts facts(const craft_sim* s) {
+  return {&s->cfg, s->n_envs, s->env_base, s->pool_capacity, s->pool_count, s->k.obs_fmt,
+          (int64_t)s->queue.size(), s->q_begun};
 }
 
 void latch(craft_sim* s, int code, int64_t slot) {
@@ -168,8 +171,6 @@ void parallel_for(const craft_sim* s, int64_t n, Fn fn) {
   }
   for (auto& th : pool) th.join();
 }
-
-int esize(int fmt) { return fmt == CRAFT_OBS_F32 ? 4 : (fmt == CRAFT_OBS_BF16 ? 2 : 1); }
 
 // The slot's current grid: its scenario's pool row minus the cells cleared this episode.
 void env_grid(const craft_sim* s, int64_t slot, int scen, uint8_t* g) {
@@ -471,80 +472,113 @@ struct TickIn {
   int32_t* label;             // craft_step_teach
 };
 
+// ---- what the three tick loops share that is not protocol (tick_slot, craft_step_lang,
+// craft_step_stream: each keeps its own protocol body) -------------------------------------------
+
+// The hashed action draw of a slot that is given no action (include/craft.h craft_step).
+int hashed_action(const craft_sim* s, uint64_t seed, int64_t slot, int64_t tick) {
+  return (int)((uint32_t)(splitmix64(seed ^ ((uint64_t)(s->env_base + slot) << 20) ^ (uint64_t)tick) >> 32) % 6u);
+}
+
+// A slot reset / set_state has initialised: an interior position on a loaded pool row.
+bool slot_valid(const craft_sim* s, const Agent& a) {
+  return a.x >= 1 && a.x <= s->W - 2 && a.y >= 1 && a.y <= s->H - 2 && a.scen < s->pool_count;
+}
+
+// What a tick writes for a slot that was never initialised (the caller latches CRAFT_EINVAL): no
+// transition, a zero observation row, the label of an error.
+void invalid_slot_outputs(const craft_sim* s, int64_t i, int8_t* code, void* obs, int32_t* label, uint8_t* row) {
+  if (code) code[i] = -1;
+  if (obs) {
+    std::memset(row, 0, s->F);
+    put_obs(s->k.obs_fmt, obs, i, s->F, row);
+  }
+  if (label) label[i] = -2;
+}
+
+// One thread's counts of a tick, and their sum over the threads into the handle's episode
+// statistics and *any_live.
 struct TickAcc {
   int64_t succ = 0, ended = 0, steps = 0;
   bool any_live = false;
 };
 
+struct TickTotals {
+  std::atomic<int64_t> succ{0}, ended{0}, steps{0};
+  std::atomic<bool> live{false};
+  void add(const TickAcc& a) {
+    succ += a.succ; ended += a.ended; steps += a.steps;
+    if (a.any_live) live = true;
+  }
+  void commit(craft_sim* s, int32_t* any_live) {
+    s->stats[0] += succ.load();
+    s->stats[1] += ended.load();
+    s->stats[2] += steps.load();
+    if (any_live && live.load()) *any_live = 1;      // only ever set to 1 (craft.h)
+  }
+};
+
 void tick_slot(craft_sim* s, int64_t i, const TickIn& in, TickAcc& acc, uint8_t* g, uint8_t* row) {
   const int64_t slot = i;
   Agent a = unpack_state(s->state[slot]);
-  bool live = !(a.x < 1 || a.x > s->W - 2 || a.y < 1 || a.y > s->H - 2 || a.scen >= s->pool_count);
-  int act = 0;
-  if (live) {
-    act = in.actions ? in.actions[slot]
-                     : (int)((uint32_t)(splitmix64(in.seed ^ ((uint64_t)(s->env_base + slot) << 20) ^
-                                                   (uint64_t)in.tick) >> 32) % 6u);
-    if (in.bc && in.bc[slot]) act = in.ref[slot];    // behaviour cloning, imitation.py:56-57
-  } else {
-    latch(s, CRAFT_EINVAL, slot);                    // never initialised by reset / set_state
+  if (!slot_valid(s, a)) {                           // never initialised by reset / set_state
+    latch(s, CRAFT_EINVAL, slot);
+    invalid_slot_outputs(s, i, in.code, in.obs, in.label, row);
+    return;
   }
+  int act = in.actions ? in.actions[slot] : hashed_action(s, in.seed, slot, in.tick);
+  if (in.bc && in.bc[slot]) act = in.ref[slot];      // behaviour cloning, imitation.py:56-57
   uint8_t* iv = s->inv.data() + 32 * slot;
   uint32_t* m = s->mask.data() + 8 * slot;
   int d = 0, succ = -1, counted = 0, code = -1;
-  if (live) {
-    env_grid(s, slot, a.scen, g);
-    bool restart = false;
-    if (a.frozen) {
-      d = 1;
-    } else {
-      counted = 1;
-      a.timer -= 1;
-      d = (act == CRAFT_STOP) || a.timer <= 0;
-      restart = d && (in.flags & CRAFT_STEP_AUTORESET);
-    }
-    if (d) succ = satisfies(s, g, iv, a, a.task);   // on the pre-step state
-    if (restart) {                                   // CraftScenario.init, craft.py:268-273
-      const uint32_t iw = s->init[slot];
-      a.x = iw & 0xff; a.y = (iw >> 8) & 0xff; a.dir = (iw >> 16) & 3;
-      a.timer = s->cfg.max_timesteps;
-      std::memset(iv, 0, 32);
-      std::memset(m, 0, 32);
-      std::memcpy(g, s->pool.data() + (size_t)a.scen * s->C, s->C);
-    } else if (d && !a.frozen) {
-      a.frozen = 1;
-      a.timer = std::max(a.timer, 0);
-    } else if (!d) {
-      if (act < 0 || act >= CRAFT_N_ACTIONS) {
-        latch(s, CRAFT_EBADACTION, slot);
-      } else {
-        const int ox = a.x, oy = a.y;
-        bool ic = false, mc = false;
-        transition(s, g, iv, a, m, act, ic, mc, slot);
-        code = transition_code(ox, oy, a, ic);
-      }
-    }
-    s->state[slot] = pack_state(a);
-    if (in.done) in.done[i] = (uint8_t)d;
-    if (in.sat) in.sat[i] = (int8_t)succ;
-    if (in.reward) in.reward[i] = (counted && d && succ == 1) ? 1.0f : 0.0f;
-    if (in.rec) in.rec[i] = counted ? act : -1;      // action_seqs, imitation.py:59-61
-    acc.succ += counted && d && succ == 1;
-    acc.ended += counted && d;
-    acc.steps += counted;
-    acc.any_live = acc.any_live || (counted && !d);
+  env_grid(s, slot, a.scen, g);
+  bool restart = false;
+  if (a.frozen) {
+    d = 1;
+  } else {
+    counted = 1;
+    a.timer -= 1;
+    d = (act == CRAFT_STOP) || a.timer <= 0;
+    restart = d && (in.flags & CRAFT_STEP_AUTORESET);
   }
+  if (d) succ = satisfies(s, g, iv, a, a.task);     // on the pre-step state
+  if (restart) {                                     // CraftScenario.init, craft.py:268-273
+    const uint32_t iw = s->init[slot];
+    a.x = iw & 0xff; a.y = (iw >> 8) & 0xff; a.dir = (iw >> 16) & 3;
+    a.timer = s->cfg.max_timesteps;
+    std::memset(iv, 0, 32);
+    std::memset(m, 0, 32);
+    std::memcpy(g, s->pool.data() + (size_t)a.scen * s->C, s->C);
+  } else if (d && !a.frozen) {
+    a.frozen = 1;
+    a.timer = std::max(a.timer, 0);
+  } else if (!d) {
+    if (act < 0 || act >= CRAFT_N_ACTIONS) {
+      latch(s, CRAFT_EBADACTION, slot);
+    } else {
+      const int ox = a.x, oy = a.y;
+      bool ic = false, mc = false;
+      transition(s, g, iv, a, m, act, ic, mc, slot);
+      code = transition_code(ox, oy, a, ic);
+    }
+  }
+  s->state[slot] = pack_state(a);
+  if (in.done) in.done[i] = (uint8_t)d;
+  if (in.sat) in.sat[i] = (int8_t)succ;
+  if (in.reward) in.reward[i] = (counted && d && succ == 1) ? 1.0f : 0.0f;
+  if (in.rec) in.rec[i] = counted ? act : -1;        // action_seqs, imitation.py:59-61
+  acc.succ += counted && d && succ == 1;
+  acc.ended += counted && d;
+  acc.steps += counted;
+  acc.any_live = acc.any_live || (counted && !d);
   if (in.code) in.code[i] = (int8_t)code;
   if (in.obs) {
-    if (live) features(s, g, iv, a, row);
-    else std::memset(row, 0, s->F);
-    put_obs(s->obs_fmt, in.obs, i, s->F, row);
+    features(s, g, iv, a, row);
+    put_obs(s->k.obs_fmt, in.obs, i, s->F, row);
   }
   if (in.label) {                                    // the teacher's label of the new state
-    int action = -2;
-    if (live && a.frozen) {
-      action = -1;                                   // imitation.py:50-51
-    } else if (live) {
+    int action = -1;                                 // a frozen slot: imitation.py:50-51
+    if (!a.frozen) {
       int len = -1, err = 0;
       action = teach(s, g, iv, a, a.task, false, len, err);
       if (err) latch(s, err, i);
@@ -554,29 +588,14 @@ void tick_slot(craft_sim* s, int64_t i, const TickIn& in, TickAcc& acc, uint8_t*
 }
 
 int run_ticks(craft_sim* s, const TickIn& in, int32_t* any_live) {
-  TickAcc tot;
-  std::atomic<int64_t> succ{0}, ended{0}, steps{0};
-  std::atomic<bool> live{false};
+  TickTotals tot;
   parallel_for(s, s->n_envs, [&](int64_t lo, int64_t hi) {
     TickAcc acc;
     std::vector<uint8_t> g(CRAFT_MAX_CELLS), row(s->F);
     for (int64_t i = lo; i < hi; ++i) tick_slot(s, i, in, acc, g.data(), row.data());
-    succ += acc.succ; ended += acc.ended; steps += acc.steps;
-    if (acc.any_live) live = true;
+    tot.add(acc);
   });
-  s->stats[0] += succ.load();
-  s->stats[1] += ended.load();
-  s->stats[2] += steps.load();
-  if (any_live && live.load()) *any_live = 1;        // only ever set to 1 (craft.h)
-  return CRAFT_OK;
-}
-
-// The checks craft_step_ex / craft_step_teach make before any work (craft_sim.hip step_args).
-int step_check(craft_sim* s, const craft_step_args_t* x) {
-  if (x->obs && (reinterpret_cast<uintptr_t>(x->obs) & 15u))
-    return fail(s, CRAFT_EINVAL, "craft_step: obs must be 16-byte aligned");
-  if (x->behavior_clone && !x->ref_actions)
-    return fail(s, CRAFT_EINVAL, "craft_step_ex: behavior_clone needs ref_actions");
+  tot.commit(s, any_live);
   return CRAFT_OK;
 }
 
@@ -645,7 +664,7 @@ int craft_sim_create(const craft_config_t* cfg, int device, int64_t n_envs, int6
   s->pool_capacity = pool_capacity;
   s->W = cfg->width; s->H = cfg->height; s->C = s->W * s->H; s->K = cfg->n_kinds; s->F = cfg->n_features;
   s->win = cfg->window_width;
-  s->tile = default_tile(s->win);
+  s->k.tile = craft_host::default_tile(s->win);
   for (auto& x : s->stats) x = 0;
   try {
     s->pool.assign((size_t)pool_capacity * s->C, 0);
@@ -683,50 +702,24 @@ int craft_sim_info(const craft_sim_t* s, int64_t* n_envs, int32_t* pool_capacity
 // shape queries; they change nothing here (there are no workgroups).
 int craft_sim_tune(craft_sim_t* s, int32_t tile_envs, int32_t max_resident_per_cu, int32_t obs_store) {
   if (!s) return CRAFT_EINVAL;
-  if (tile_envs == 0) tile_envs = default_tile(s->win);
-  if (tile_envs != 16 && tile_envs != 32 && tile_envs != 64)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune: tile_envs must be 16, 32 or 64");
-  if (max_resident_per_cu != 0 && (max_resident_per_cu < 3 || max_resident_per_cu > 32))
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune: max_resident_per_cu must be 0 or 3..32");
-  if (obs_store < 0 || obs_store > 2)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune: obs_store must be 0 (write-back), 1 (nontemporal) or 2 (write-through)");
-  s->tile = tile_envs;
-  s->resident_cap = max_resident_per_cu;
-  s->obs_store = obs_store;
-  return CRAFT_OK;
+  return craft_host::set_tune(s->k, s->win, tile_envs, max_resident_per_cu, obs_store, s->last_error);
 }
 
 int craft_sim_tune_rollout(craft_sim_t* s, int32_t chunk_ticks, int32_t threads) {
   if (!s) return CRAFT_EINVAL;
-  if (chunk_ticks < -1 || chunk_ticks > 4096)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_rollout: chunk_ticks must be -1..4096");
-  if (threads != 0 && threads != 128 && threads != 256 && threads != 320 && threads != 384 && threads != 512)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_rollout: threads must be 0, 128, 256, 320, 384 or 512");
-  s->rollout_chunk = chunk_ticks;
-  s->rollout_threads = threads;
-  return CRAFT_OK;
+  return craft_host::set_tune_rollout(s->k, chunk_ticks, threads, s->last_error);
 }
 
 int craft_sim_tune_teach(craft_sim_t* s, int32_t kernel, int32_t lanes, int32_t table) {
-  if (!s) return CRAFT_EINVAL;
-  if (kernel < 0 || kernel > 2)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_teach: kernel must be 0 (auto), 1 (one-tile) or 2 (two-tile)");
-  if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_teach: lanes must be 0 (default), 1, 2 or 4");
-  if (table < 0 || table > 2)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_teach: table must be 0 (auto), 1 (always) or 2 (never)");
-  s->teach_kernel = kernel;
-  s->teach_lanes = lanes;
-  s->teach_table = table;      // (this variant keeps no table: every query runs the BFS)
-  return CRAFT_OK;
+  if (!s) return CRAFT_EINVAL;   // (this variant keeps no table: every query runs the BFS)
+  return craft_host::set_tune_teach(s->k, kernel, lanes, table, s->last_error);
 }
 
 int craft_abi_version(void) { return CRAFT_ABI_VERSION; }
 
 int craft_sim_tune_host(craft_sim_t* s, int32_t threads) {
   if (!s) return CRAFT_EINVAL;
-  if (threads < 0 || threads > 1024)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_host: threads must be 0 (the machine's) or 1..1024");
+  if (const int rc = craft_host::check_tune_host(threads, s->last_error)) return rc;
   s->threads = threads ? threads : hw_threads();
   return CRAFT_OK;
 }
@@ -738,32 +731,29 @@ int craft_sim_sync_table(craft_sim_t* s, void* /*stream*/) {
 int craft_sim_step_shape(const craft_sim_t* s, int32_t teach, int32_t* kernel, int32_t* envs, int32_t* lanes) {
   if (!s) return CRAFT_EINVAL;
   if (kernel) *kernel = CRAFT_KERNEL_TILE;
-  if (envs) *envs = s->tile;
+  if (envs) *envs = s->k.tile;
   if (lanes) *lanes = teach ? 1 : 0;
   return CRAFT_OK;
 }
 
 int craft_sim_rollout_shape(const craft_sim_t* s, int32_t* tile_envs, int32_t* threads, int32_t* split) {
   if (!s) return CRAFT_EINVAL;
-  if (tile_envs) *tile_envs = s->tile;
-  if (threads) *threads = s->rollout_threads;
+  if (tile_envs) *tile_envs = s->k.tile;
+  if (threads) *threads = s->k.rollout_threads;
   if (split) *split = 0;
   return CRAFT_OK;
 }
 
 int craft_sim_tile_shape(const craft_sim_t* s, int32_t* tile_envs, int32_t* obs_store) {
   if (!s) return CRAFT_EINVAL;
-  if (tile_envs) *tile_envs = s->tile;
-  if (obs_store) *obs_store = s->obs_store;
+  if (tile_envs) *tile_envs = s->k.tile;
+  if (obs_store) *obs_store = s->k.obs_store;
   return CRAFT_OK;
 }
 
 int craft_sim_set_obs_format(craft_sim_t* s, int32_t format) {
   if (!s) return CRAFT_EINVAL;
-  if (format != CRAFT_OBS_F32 && format != CRAFT_OBS_BF16 && format != CRAFT_OBS_U8)
-    return fail(s, CRAFT_EINVAL, "craft_sim_set_obs_format: format must be 0 (fp32), 1 (bf16) or 2 (u8)");
-  s->obs_fmt = format;
-  return CRAFT_OK;
+  return craft_host::set_obs_format(s->k, format, s->last_error);
 }
 
 int craft_sim_check(craft_sim_t* s, int64_t* env_out, void* /*stream*/) {
@@ -790,8 +780,8 @@ int craft_sim_error_word(craft_sim_t* s, int32_t* out, void* /*stream*/) {
 }
 
 int craft_pool_load(craft_sim_t* s, const uint8_t* grids, int32_t first, int32_t count) {
-  if (!s || !grids || first < 0 || count < 0) return fail(s, CRAFT_EINVAL, "craft_pool_load: bad argument");
-  if ((int64_t)first + count > s->pool_capacity) return fail(s, CRAFT_ERANGE, "craft_pool_load: beyond pool capacity");
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_pool_load(facts(s), grids, first, count, s->last_error)) return rc;
   std::vector<uint8_t> conn((size_t)count, 0);
   for (int p = 0; p < count; ++p) {             // every row is checked before any is written
     std::string msg;
@@ -812,19 +802,12 @@ int craft_pool_generate(craft_sim_t* s, uint64_t seed, int64_t scenario_id0, int
                         int32_t boundary_kind, const int32_t* primitives, int32_t n_primitive_kinds,
                         int32_t n_per_primitive, const int32_t* workshop_kind, int32_t n_workshops,
                         int32_t* init_pos_out, void* /*stream*/) {
-  if (!s || first < 0 || count < 0 || n_primitive_kinds < 0 || n_primitive_kinds > 8 || n_per_primitive < 0 ||
-      n_workshops < 0 || n_workshops > 8 || (n_primitive_kinds && !primitives) || (n_workshops && !workshop_kind))
-    return fail(s, CRAFT_EINVAL, "craft_pool_generate: bad argument");
-  if ((int64_t)first + count > s->pool_capacity) return fail(s, CRAFT_ERANGE, "craft_pool_generate: beyond pool capacity");
-  const int K = s->K, W = s->W, H = s->H, C = s->C;
-  auto bad_kind = [&](int k) { return k <= 0 || k >= K; };
-  if (bad_kind(boundary_kind)) return fail(s, CRAFT_EINVAL, "craft_pool_generate: bad boundary kind");
-  for (int i = 0; i < n_primitive_kinds; ++i)
-    if (bad_kind(primitives[i])) return fail(s, CRAFT_EINVAL, "craft_pool_generate: bad primitive kind");
-  for (int i = 0; i < n_workshops; ++i)
-    if (bad_kind(workshop_kind[i])) return fail(s, CRAFT_EINVAL, "craft_pool_generate: bad workshop kind");
-  if ((int64_t)n_primitive_kinds * n_per_primitive + n_workshops + 1 > (int64_t)(W - 2) * (H - 2))
-    return fail(s, CRAFT_EINVAL, "craft_pool_generate: more objects than interior cells");
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_pool_generate(facts(s), first, count, boundary_kind, primitives,
+                                                     n_primitive_kinds, n_per_primitive, workshop_kind, n_workshops,
+                                                     s->last_error))
+    return rc;
+  const int W = s->W, H = s->H, C = s->C;
   const Bits valid = brange(0, C);
   Bits border = bzero();
   for (int c = 0; c < C; ++c) {
@@ -898,8 +881,8 @@ int craft_pool_generate(craft_sim_t* s, uint64_t seed, int64_t scenario_id0, int
 
 int craft_reset(craft_sim_t* s, const int32_t* scenario, const int32_t* pos_x, const int32_t* pos_y,
                 const int32_t* dir, const int32_t* task, void* obs, void* /*stream*/) {
-  if (!s || !scenario || !pos_x || !pos_y || !dir || !task) return fail(s, CRAFT_EINVAL, "craft_reset: null input");
-  if (obs && (reinterpret_cast<uintptr_t>(obs) & 15u)) return fail(s, CRAFT_EINVAL, "craft_reset: obs must be 16-byte aligned");
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_reset(scenario, pos_x, pos_y, dir, task, obs, s->last_error)) return rc;
   parallel_for(s, s->n_envs, [&](int64_t lo, int64_t hi) {
     std::vector<uint8_t> g(CRAFT_MAX_CELLS), row(s->F);
     for (int64_t i = lo; i < hi; ++i) {             // CraftScenario.init, craft.py:262-273
@@ -922,7 +905,7 @@ int craft_reset(craft_sim_t* s, const int32_t* scenario, const int32_t* pos_x, c
         } else {
           std::memset(row.data(), 0, s->F);
         }
-        put_obs(s->obs_fmt, obs, i, s->F, row.data());
+        put_obs(s->k.obs_fmt, obs, i, s->F, row.data());
       }
     }
   });
@@ -932,8 +915,7 @@ int craft_reset(craft_sim_t* s, const int32_t* scenario, const int32_t* pos_x, c
 
 int craft_step_ex(craft_sim_t* s, const craft_step_args_t* x, void* /*stream*/) {
   if (!s || !x) return CRAFT_EINVAL;
-  const int rc = step_check(s, x);
-  if (rc) return rc;
+  if (const int rc = craft_host::check_step(x, s->last_error)) return rc;
   return run_ticks(s, tick_in(x), x->any_live);
 }
 
@@ -947,10 +929,7 @@ int craft_step(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, int
 
 int craft_step_teach(craft_sim_t* s, const craft_step_args_t* x, int32_t* label_out, void* /*stream*/) {
   if (!s || !x || !label_out) return CRAFT_EINVAL;
-  if (4 * s->C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_step_teach: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
-  const int rc = step_check(s, x);
-  if (rc) return rc;
+  if (const int rc = craft_host::check_step_teach(facts(s), x, s->last_error)) return rc;
   TickIn in = tick_in(x);
   in.label = label_out;
   return run_ticks(s, in, x->any_live);
@@ -961,29 +940,16 @@ int craft_step_teach(craft_sim_t* s, const craft_step_args_t* x, int32_t* label_
 // read off the new state, the teacher on every slot that was running before the tick.
 int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* /*stream*/) {
   if (!s || !x) return CRAFT_EINVAL;
-  if (x->flags != 0) return fail(s, CRAFT_EINVAL, "craft_step_lang: flags must be 0 (no auto-reset in this protocol)");
-  if (x->use_alt && !x->alt_actions) return fail(s, CRAFT_EINVAL, "craft_step_lang: use_alt needs alt_actions");
-  if (x->obs && (reinterpret_cast<uintptr_t>(x->obs) & 15u))
-    return fail(s, CRAFT_EINVAL, "craft_step_lang: obs must be 16-byte aligned");
-  if (x->label_out && 4 * s->C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_step_lang: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
-  std::atomic<int64_t> n_succ{0}, n_ended{0}, n_steps{0};
-  std::atomic<bool> running{false};
+  if (const int rc = craft_host::check_step_lang(facts(s), x, s->last_error)) return rc;
+  TickTotals tot;
   parallel_for(s, s->n_envs, [&](int64_t lo, int64_t hi) {
-    int64_t succs = 0, ended = 0, steps = 0;
-    bool some_running = false;
+    TickAcc acc;
     std::vector<uint8_t> g(CRAFT_MAX_CELLS), row(s->F);
     for (int64_t i = lo; i < hi; ++i) {
       Agent a = unpack_state(s->state[i]);
-      const bool valid = a.x >= 1 && a.x <= s->W - 2 && a.y >= 1 && a.y <= s->H - 2 && a.scen < s->pool_count;
-      if (!valid) {                                    // never initialised by reset / set_state
+      if (!slot_valid(s, a)) {                         // never initialised by reset / set_state
         latch(s, CRAFT_EINVAL, i);
-        if (x->transition_code) x->transition_code[i] = -1;
-        if (x->obs) {
-          std::memset(row.data(), 0, s->F);
-          put_obs(s->obs_fmt, x->obs, i, s->F, row.data());
-        }
-        if (x->label_out) x->label_out[i] = -2;
+        invalid_slot_outputs(s, i, x->transition_code, x->obs, x->label_out, row.data());
         continue;
       }
       uint8_t* iv = s->inv.data() + 32 * i;
@@ -995,8 +961,7 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* /*str
         asked = x->use_alt && x->use_alt[i];
         if (asked) action = x->alt_actions[i];
         else if (x->actions) action = x->actions[i];
-        else action = (int)((uint32_t)(splitmix64(x->action_seed ^ ((uint64_t)(s->env_base + i) << 20) ^
-                                                  (uint64_t)x->tick) >> 32) % 6u);
+        else action = hashed_action(s, x->action_seed, i, x->tick);
         if (action < 0 || action >= CRAFT_N_ACTIONS) {
           latch(s, CRAFT_EBADACTION, i);
         } else {
@@ -1020,13 +985,13 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* /*str
       if (x->action_record) x->action_record[i] = stepped ? action : -1;
       if (x->ask_record) x->ask_record[i] = (int8_t)(stepped ? (asked ? 1 : 0) : -1);
       if (x->transition_code) x->transition_code[i] = (int8_t)code;
-      steps += stepped;
-      ended += stepped && done_now;
-      succs += stepped && done_now && sat == 1;
-      some_running = some_running || (stepped && !done_now);
+      acc.steps += stepped;
+      acc.ended += stepped && done_now;
+      acc.succ += stepped && done_now && sat == 1;
+      acc.any_live = acc.any_live || (stepped && !done_now);
       if (x->obs) {
         features(s, g.data(), iv, a, row.data());
-        put_obs(s->obs_fmt, x->obs, i, s->F, row.data());
+        put_obs(s->k.obs_fmt, x->obs, i, s->F, row.data());
       }
       if (x->label_out) {
         int label = -1;                                // done before the tick
@@ -1038,13 +1003,9 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* /*str
         x->label_out[i] = label;
       }
     }
-    n_succ += succs; n_ended += ended; n_steps += steps;
-    if (some_running) running = true;
+    tot.add(acc);
   });
-  s->stats[0] += n_succ.load();
-  s->stats[1] += n_ended.load();
-  s->stats[2] += n_steps.load();
-  if (x->any_live && running.load()) *x->any_live = 1;
+  tot.commit(s, x->any_live);
   return CRAFT_OK;
 }
 
@@ -1054,16 +1015,13 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* /*str
 
 int craft_episode_queue(craft_sim_t* s, const int32_t* specs, int64_t count) {
   if (!s) return CRAFT_EINVAL;
-  if (!specs || count < 1 || count > (int64_t)INT32_MAX)
-    return fail(s, CRAFT_EINVAL, "craft_episode_queue: specs must hold 1 .. 2^31 - 1 entries");
+  if (const int rc = craft_host::check_episode_queue(specs, count, s->last_error)) return rc;
   std::vector<craft_sim::QueueEntry> q((size_t)count);
   for (int64_t i = 0; i < count; ++i) {
     const int32_t* e = specs + 5 * i;
     const bool ok = e[0] >= 0 && e[0] < s->pool_count && e[1] >= 1 && e[1] <= s->W - 2 && e[2] >= 1 &&
                     e[2] <= s->H - 2 && e[3] >= 0 && e[3] <= 3 && e[4] >= 0 && e[4] < s->cfg.n_tasks;
-    if (!ok)                                          // the queue installed before stays in force
-      return fail(s, CRAFT_EINVAL, "craft_episode_queue: entry " + std::to_string(i) +
-                                       " is invalid (scenario, position, direction or task out of range)");
+    if (!ok) return craft_host::queue_entry_invalid((uint64_t)i, s->last_error);   // the old queue stays in force
     q[(size_t)i] = {e[0], e[1], e[2], e[3], e[4]};
   }
   s->queue.swap(q);
@@ -1073,19 +1031,9 @@ int craft_episode_queue(craft_sim_t* s, const int32_t* specs, int64_t count) {
 
 int craft_episode_begin(craft_sim_t* s, int64_t first, int64_t stride, uint32_t flags, void* obs, void* stream) {
   if (!s) return CRAFT_EINVAL;
-  if (s->queue.empty()) return fail(s, CRAFT_EINVAL, "craft_episode_begin: no episode queue installed (craft_episode_queue)");
-  if (stride < 1) return fail(s, CRAFT_EINVAL, "craft_episode_begin: stride must be >= 1");
-  if (first < 0) return fail(s, CRAFT_EINVAL, "craft_episode_begin: first must be >= 0");
-  if (flags & ~CRAFT_QUEUE_WRAP) return fail(s, CRAFT_EINVAL, "craft_episode_begin: unknown flag");
-  if (obs && (reinterpret_cast<uintptr_t>(obs) & 15u))
-    return fail(s, CRAFT_EINVAL, "craft_episode_begin: obs must be 16-byte aligned");
+  if (const int rc = craft_host::check_episode_begin(facts(s), first, stride, flags, obs, s->last_error)) return rc;
   const bool wrap = (flags & CRAFT_QUEUE_WRAP) != 0;
-  const int64_t count = (int64_t)s->queue.size(), n = s->n_envs;
-  if (first > INT64_MAX - s->env_base - n) return fail(s, CRAFT_EINVAL, "craft_episode_begin: first is out of range");
-  const int64_t g0 = first + s->env_base;
-  if (!wrap && n > 0 && g0 + n - 1 >= count)
-    return fail(s, CRAFT_EINVAL, "craft_episode_begin: slot " + std::to_string(std::max<int64_t>(count - g0, 0)) +
-                                     " would start past the end of the queue (" + std::to_string(count) + " entries)");
+  const int64_t count = (int64_t)s->queue.size(), n = s->n_envs, g0 = first + s->env_base;
   s->cursor.assign((size_t)n, -1);
   std::vector<int32_t> r((size_t)(5 * n));
   for (int64_t i = 0; i < n; ++i) {
@@ -1105,37 +1053,20 @@ int craft_episode_begin(craft_sim_t* s, int64_t first, int64_t stride, uint32_t 
 int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* /*stream*/) {
   if (!s || !x) return CRAFT_EINVAL;
   const craft_step_args_t& p = x->step;
-  if (p.flags != CRAFT_STEP_AUTORESET)
-    return fail(s, CRAFT_EINVAL, "craft_step_stream: step.flags must be CRAFT_STEP_AUTORESET");
-  if (s->queue.empty() || !s->q_begun)
-    return fail(s, CRAFT_EINVAL, "craft_step_stream: craft_episode_begin has not put the slots on the queue");
-  if (x->label_out && 4 * s->C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_step_stream: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
-  const int rc = step_check(s, &p);
-  if (rc) return rc;
+  if (const int rc = craft_host::check_step_stream(facts(s), x, s->last_error)) return rc;
   const int64_t count = (int64_t)s->queue.size();
-  std::atomic<int64_t> n_succ{0}, n_ended{0}, n_steps{0};
-  std::atomic<bool> running{false};
+  TickTotals tot;
   parallel_for(s, s->n_envs, [&](int64_t lo, int64_t hi) {
-    int64_t succs = 0, ended = 0, steps = 0;
-    bool some_running = false;
+    TickAcc acc;
     std::vector<uint8_t> g(CRAFT_MAX_CELLS), row(s->F);
     for (int64_t i = lo; i < hi; ++i) {
       Agent a = unpack_state(s->state[i]);
-      const bool valid = a.x >= 1 && a.x <= s->W - 2 && a.y >= 1 && a.y <= s->H - 2 && a.scen < s->pool_count;
-      if (!valid) {                                    // never initialised by reset / set_state
+      if (!slot_valid(s, a)) {                         // never initialised by reset / set_state
         latch(s, CRAFT_EINVAL, i);
-        if (p.transition_code) p.transition_code[i] = -1;
-        if (p.obs) {
-          std::memset(row.data(), 0, s->F);
-          put_obs(s->obs_fmt, p.obs, i, s->F, row.data());
-        }
-        if (x->label_out) x->label_out[i] = -2;
+        invalid_slot_outputs(s, i, p.transition_code, p.obs, x->label_out, row.data());
         continue;
       }
-      int action = p.actions ? p.actions[i]
-                             : (int)((uint32_t)(splitmix64(p.action_seed ^ ((uint64_t)(s->env_base + i) << 20) ^
-                                                           (uint64_t)p.tick) >> 32) % 6u);
+      int action = p.actions ? p.actions[i] : hashed_action(s, p.action_seed, i, p.tick);
       if (p.behavior_clone && p.behavior_clone[i]) action = p.ref_actions[i];
       uint8_t* iv = s->inv.data() + 32 * i;
       uint32_t* m = s->mask.data() + 8 * i;
@@ -1192,13 +1123,13 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* /
       if (x->episode_end) x->episode_end[i] = ended_index;
       if (x->end_pose) x->end_pose[i] = ended_pose;
       if (x->episode_now) x->episode_now[i] = a.frozen ? -1 : (int32_t)s->cursor[(size_t)i];
-      steps += ran;
-      ended += ends;
-      succs += ends && sat == 1;
-      some_running = some_running || !a.frozen;
+      acc.steps += ran;
+      acc.ended += ends;
+      acc.succ += ends && sat == 1;
+      acc.any_live = acc.any_live || !a.frozen;
       if (p.obs) {
         features(s, g.data(), iv, a, row.data());
-        put_obs(s->obs_fmt, p.obs, i, s->F, row.data());
+        put_obs(s->k.obs_fmt, p.obs, i, s->F, row.data());
       }
       if (x->label_out) {
         int label = -1;                                // a frozen slot: imitation.py:50-51
@@ -1210,13 +1141,9 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* /
         x->label_out[i] = label;
       }
     }
-    n_succ += succs; n_ended += ended; n_steps += steps;
-    if (some_running) running = true;
+    tot.add(acc);
   });
-  s->stats[0] += n_succ.load();
-  s->stats[1] += n_ended.load();
-  s->stats[2] += n_steps.load();
-  if (p.any_live && running.load()) *p.any_live = 1;
+  tot.commit(s, p.any_live);
   return CRAFT_OK;
 }
 
@@ -1224,11 +1151,8 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
                   uint32_t flags, void* obs, int32_t ring, float* reward, uint8_t* done, int8_t* success,
                   void* /*stream*/) {
   if (!s) return CRAFT_EINVAL;
-  if (n_ticks < 0 || ring < 1 || tick0 < 0)
-    return fail(s, CRAFT_EINVAL, "craft_rollout: need n_ticks >= 0, ring >= 1, tick0 >= 0");
-  const int esz = esize(s->obs_fmt);
-  if (obs && ((reinterpret_cast<uintptr_t>(obs) & 15u) || (ring > 1 && (s->n_envs * (int64_t)s->F * esz) % 16 != 0)))
-    return fail(s, CRAFT_EINVAL, "craft_rollout: every obs ring slot must be 16-byte aligned");
+  if (const int rc = craft_host::check_rollout(facts(s), tick0, n_ticks, ring, obs, s->last_error)) return rc;
+  const int esz = craft_host::obs_elem_size(s->k.obs_fmt);
   const int64_t n = s->n_envs;
   for (int32_t k = 0; k < n_ticks; ++k) {
     const int64_t r = (tick0 + k) % ring;            // tick t writes ring slot t % ring
@@ -1250,17 +1174,9 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
 // tick's label-source slots (make_data.get_reference_actions, imitation.py:47-57)
 int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, void* /*stream*/) {
   if (!s || !x) return CRAFT_EINVAL;
-  if (x->n_ticks < 0 || x->ring < 1 || x->tick0 < 0)
-    return fail(s, CRAFT_EINVAL, "craft_rollout_teach: need n_ticks >= 0, ring >= 1, tick0 >= 0");
-  if (4 * s->C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_rollout_teach: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  if (const int rc = craft_host::check_rollout_teach(facts(s), x, s->last_error)) return rc;
   const bool lsync = x->label_actions != 0 || x->behavior_clone != nullptr;
-  if (lsync && !x->label_in)
-    return fail(s, CRAFT_EINVAL, "craft_rollout_teach: label_actions / behavior_clone need label_in");
-  const int esz = esize(s->obs_fmt);
-  if (x->obs && ((reinterpret_cast<uintptr_t>(x->obs) & 15u) ||
-                 (x->ring > 1 && (s->n_envs * (int64_t)s->F * esz) % 16 != 0)))
-    return fail(s, CRAFT_EINVAL, "craft_rollout_teach: every obs ring slot must be 16-byte aligned");
+  const int esz = craft_host::obs_elem_size(s->k.obs_fmt);
   const int64_t n = s->n_envs;
   std::vector<int32_t> cur(n, 0), lab(n, 0);
   std::vector<uint8_t> src(n, 0);                    // 1: the slot acts on its label
@@ -1300,8 +1216,7 @@ int craft_transition(craft_sim_t* s, const int32_t* src, const int32_t* dst, con
                      int8_t* code_out, void* /*stream*/) {
   if (!s) return CRAFT_EINVAL;
   if (n == 0) return CRAFT_OK;
-  if (!actions || n < 0) return fail(s, CRAFT_EINVAL, "craft_transition: bad argument");
-  if (!src && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_transition: n > n_envs");
+  if (const int rc = craft_host::check_transition(facts(s), src, actions, n, s->last_error)) return rc;
   parallel_for(s, n, [&](int64_t lo, int64_t hi) {
     std::vector<uint8_t> g(CRAFT_MAX_CELLS);
     for (int64_t i = lo; i < hi; ++i) {              // CraftState.step, craft.py:332-424
@@ -1311,7 +1226,7 @@ int craft_transition(craft_sim_t* s, const int32_t* src, const int32_t* dst, con
         latch(s, CRAFT_ERANGE, i);
       } else {
         Agent a = unpack_state(s->state[slot]);
-        if (a.x < 1 || a.x > s->W - 2 || a.y < 1 || a.y > s->H - 2 || a.scen >= s->pool_count) {
+        if (!slot_valid(s, a)) {
           latch(s, CRAFT_EINVAL, slot);
         } else {
           uint8_t iv[32];
@@ -1344,9 +1259,7 @@ int craft_observe(craft_sim_t* s, const int32_t* slots, int64_t n, const int32_t
                   void* /*stream*/) {
   if (!s) return CRAFT_EINVAL;
   if (n == 0) return CRAFT_OK;
-  if (n < 0) return fail(s, CRAFT_EINVAL, "craft_observe: bad argument");
-  if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_observe: n > n_envs");
-  if (obs && (reinterpret_cast<uintptr_t>(obs) & 15u)) return fail(s, CRAFT_EINVAL, "craft_observe: obs must be 16-byte aligned");
+  if (const int rc = craft_host::check_observe(facts(s), slots, n, obs, s->last_error)) return rc;
   parallel_for(s, n, [&](int64_t lo, int64_t hi) {
     std::vector<uint8_t> g(CRAFT_MAX_CELLS), row(s->F);
     for (int64_t i = lo; i < hi; ++i) {              // features() / satisfies(), craft.py:285-330
@@ -1357,7 +1270,7 @@ int craft_observe(craft_sim_t* s, const int32_t* slots, int64_t n, const int32_t
         latch(s, CRAFT_ERANGE, i);
       } else {
         a = unpack_state(s->state[slot]);
-        if (a.x < 1 || a.x > s->W - 2 || a.y < 1 || a.y > s->H - 2 || a.scen >= s->pool_count) {
+        if (!slot_valid(s, a)) {
           latch(s, CRAFT_EINVAL, slot);
           live = false;
         }
@@ -1378,7 +1291,7 @@ int craft_observe(craft_sim_t* s, const int32_t* slots, int64_t n, const int32_t
       } else if (obs) {
         std::memset(row.data(), 0, s->F);
       }
-      if (obs) put_obs(s->obs_fmt, obs, i, s->F, row.data());
+      if (obs) put_obs(s->k.obs_fmt, obs, i, s->F, row.data());
     }
   });
   return CRAFT_OK;
@@ -1388,11 +1301,9 @@ int craft_rollout_distances(craft_sim_t* s, const int32_t* tasks, const int8_t* 
                             int32_t ticks, int32_t* distances_out, uint8_t* is_get_out, int32_t* n_actions_out,
                             int32_t* flags_out, void* /*stream*/) {
   if (!s) return CRAFT_EINVAL;
-  if (!tasks || !success || !distances_out || !is_get_out || !n_actions_out || !flags_out || ticks < 0 ||
-      (ticks > 0 && !action_seqs))
-    return fail(s, CRAFT_EINVAL, "craft_rollout_distances: bad argument");
-  if (4 * s->C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_rollout_distances: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  if (const int rc = craft_host::check_rollout_distances(facts(s), tasks, success, action_seqs, ticks, distances_out,
+                                                         is_get_out, n_actions_out, flags_out, s->last_error))
+    return rc;
   std::atomic<int32_t> f0{0}, f1{0};
   parallel_for(s, s->n_envs, [&](int64_t lo, int64_t hi) {
     for (int64_t i = lo; i < hi; ++i) {              // trainers/imitation.py:79-91
@@ -1415,7 +1326,7 @@ int craft_rollout_distances(craft_sim_t* s, const int32_t* tasks, const int8_t* 
         d = -1;
       } else if (is_get && succ == 0) {
         const Agent a = unpack_state(s->state[i]);
-        if (a.x < 1 || a.x > s->W - 2 || a.y < 1 || a.y > s->H - 2 || a.scen >= s->pool_count) {
+        if (!slot_valid(s, a)) {
           latch(s, CRAFT_EINVAL, i);
           d = -2;
         } else {                                     // world.init_state(grid, pos, dir): the pool row
@@ -1440,10 +1351,7 @@ int craft_teacher(craft_sim_t* s, const int32_t* slots, int64_t n, const int32_t
                   int32_t* path_len_out, void* /*stream*/) {
   if (!s) return CRAFT_EINVAL;
   if (n == 0) return CRAFT_OK;
-  if (!action_out || n < 0) return fail(s, CRAFT_EINVAL, "craft_teacher: bad argument");
-  if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_teacher: n > n_envs");
-  if (4 * s->C > 1000)
-    return fail(s, CRAFT_EINVAL, "craft_teacher: 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
+  if (const int rc = craft_host::check_teacher(facts(s), slots, n, action_out, s->last_error)) return rc;
   parallel_for(s, n, [&](int64_t lo, int64_t hi) {
     std::vector<uint8_t> g(CRAFT_MAX_CELLS);
     for (int64_t i = lo; i < hi; ++i) {              // DemonstrationTeacher.__call__
@@ -1457,8 +1365,7 @@ int craft_teacher(craft_sim_t* s, const int32_t* slots, int64_t n, const int32_t
       const Agent a = unpack_state(s->state[slot]);
       if (a.frozen) { put(-1, -1); continue; }       // imitation.py:50-51
       const int task = tasks ? tasks[i] : a.task;
-      if (task < 0 || task >= s->cfg.n_tasks || a.x < 1 || a.x > s->W - 2 || a.y < 1 || a.y > s->H - 2 ||
-          a.scen >= s->pool_count) {
+      if (task < 0 || task >= s->cfg.n_tasks || !slot_valid(s, a)) {
         latch(s, task < 0 || task >= s->cfg.n_tasks ? CRAFT_ERANGE : CRAFT_EINVAL, i);
         put(-2, -2);
         continue;
@@ -1478,8 +1385,7 @@ int craft_get_state(craft_sim_t* s, const int32_t* slots, int64_t n, int32_t* ag
                     uint8_t* grid, int32_t* spec, void* /*stream*/) {
   if (!s) return CRAFT_EINVAL;
   if (n == 0) return CRAFT_OK;
-  if (n < 0) return fail(s, CRAFT_EINVAL, "craft_get_state: bad argument");
-  if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_get_state: n > n_envs");
+  if (const int rc = craft_host::check_get_state(facts(s), slots, n, s->last_error)) return rc;
   for (int64_t i = 0; i < n; ++i) {
     const int64_t slot = slots ? (int64_t)slots[i] : i;
     if (slot < 0 || slot >= s->n_envs) { latch(s, CRAFT_ERANGE, i); continue; }
@@ -1504,8 +1410,7 @@ int craft_set_state(craft_sim_t* s, const int32_t* slots, int64_t n, const int32
                     const int32_t* inventory, void* /*stream*/) {
   if (!s) return CRAFT_EINVAL;
   if (n == 0) return CRAFT_OK;
-  if (n < 0 || !spec || !agent) return fail(s, CRAFT_EINVAL, "craft_set_state: bad argument");
-  if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_set_state: n > n_envs");
+  if (const int rc = craft_host::check_set_state(facts(s), slots, n, spec, agent, s->last_error)) return rc;
   for (int64_t i = 0; i < n; ++i) {
     const int64_t slot = slots ? (int64_t)slots[i] : i;
     if (slot < 0 || slot >= s->n_envs) { latch(s, CRAFT_ERANGE, i); continue; }

@@ -1,14 +1,17 @@
 // craft_host.h — host-side pieces shared by the two implementations of include/craft.h: the
 // HIP library (craft_sim.hip, libpsketch_craft.so) and its CPU variant (craft_cpu.cpp,
-// libpsketch_craft_cpu.so, host pointers).  Plain C++: configuration checks, the packed task
-// table, the scenario-grid checks of craft_pool_load and the status strings, so both libraries
-// accept and refuse exactly the same inputs with the same messages.
+// libpsketch_craft_cpu.so, host pointers).  Plain C++: configuration checks, every entry point's
+// argument checks and the validated tuning knobs (craft_checks.h), the packed task table, the
+// scenario-grid checks of craft_pool_load and the status strings, so both libraries accept and
+// refuse exactly the same inputs, in the same order, with the same messages, and a refused call
+// leaves either handle as it was.
 #pragma once
 #include <cstdint>
 #include <string>
 #include <vector>
 
 #include "../../include/craft.h"
+#include "craft_checks.h"
 
 namespace craft_host {
 

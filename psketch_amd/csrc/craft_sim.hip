@@ -145,19 +145,13 @@ struct craft_sim {
   // pool rows loaded since the table was last built: craft_pool_load only records them, and the
   // next launch that reads the table builds their entries first, on its own stream
   std::vector<std::pair<int32_t, int32_t>> tt_dirty;
-  // craft_sim_tune_teach: which teacher reads the table (0 auto: craft_step_teach when the launch
-  // rewrites the previous launch's observation buffer, as a trainer's loop does, every other
-  // teacher always; 1 always; 2 never), and teacher lanes per query (0 = each kernel's default)
-  int teach_table = 0;
   bool hint_walk = false;           // some task keeps the hint walk (no hint table: craft_host.h)
-  int teach_lanes = 0;
   int32_t tt_kinds[16] = {};        // its slots' target kinds
   SimView view{};
-  int tile = craft::kMaxTileEnvs;   // envs per tile workgroup
-  int tile_knob = 0;                // craft_sim_tune's tile_envs (0 = each kernel's default)
-  int resident_cap = 0;             // 0: no cap on tile workgroups per CU
-  int rollout_chunk = 0;            // craft_rollout ticks per work unit (0: the whole launch)
-  int rollout_threads = 0;          // craft_rollout threads per tile workgroup (0: 8 per env)
+  // The validated knobs (craft_checks.h).  k.teach_table, craft_sim_tune_teach: which teacher reads
+  // the table (0 auto: craft_step_teach when the launch rewrites the previous launch's observation
+  // buffer, as a trainer's loop does, every other teacher always; 1 always; 2 never).
+  craft_host::Knobs k;
   uint8_t* d_sync = nullptr;        // craft_rollout: work-unit counter + per-tile chunk flags
   uint8_t* d_sync_graph = nullptr;  // the same for launches captured into a HIP graph
   size_t sync_bytes = 0;
@@ -165,7 +159,6 @@ struct craft_sim {
   int rollout_obs_policy = 2;       // craft_rollout's observation stores until craft_sim_tune sets one:
                                     // write-through, 1.5 % faster than write-back (tools/ab_store.sh)
   bool obs_store_tuned = false;     // craft_sim_tune chose the store policy for every kernel
-  int teach_kernel = 0;             // craft_sim_tune_teach: 0 auto, 1 one-tile, 2 two-tile
   uint64_t queue1_next = 0;         // queue[1] (the split kernel's per-unit path) at the next launch
   uint64_t queue_next = 0;          // the counter's value at the next launch (every launch adds
                                     // its units + its grid: one fetch past the end per workgroup)
@@ -199,13 +192,11 @@ int hip_fail(craft_sim* sim, hipError_t e, const char* what) {
 
 using craft_host::validate_config;
 
-// The tile kernel's default envs per workgroup (craft_sim_create, craft_sim_tune(0, ...)).
-int default_tile(int win) {
-  // 3x3: 64-env tiles; 5x5: 32 (35 KB of rows); 7x7: 32 (67 KB), 3 % faster than 16 at 16x16
-  return win == 3 ? 64 : 32;
+// What the shared argument checks (craft_checks.h) read of the handle.
+craft_host::Facts facts(const craft_sim* s) {
+  return {&s->cfg, s->n_envs, s->env_base, s->pool_capacity, s->pool_count, s->k.obs_fmt,
+          s->d_queue ? s->q_count : 0, s->q_begun};
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // LDS bytes per tile workgroup (the tile kernel's, craft_tile.h, or with two observation buffers and
 // the pristine rows the rollout kernels'); a residency cap R pads the request to 160 KiB / R
@@ -214,8 +205,8 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 size_t lds_bytes(const craft_sim* s, int tile, int obs_bufs = 1, bool pristine = false) {
   const SimView& v = s->view;
   size_t b = (size_t)craft::lds_layout(tile, v.GS, v.F, obs_bufs, pristine).bytes;
-  if (s->resident_cap > 0) {
-    const size_t capped = ((size_t)163840 / s->resident_cap) & ~size_t(15);
+  if (s->k.resident_cap > 0) {
+    const size_t capped = ((size_t)163840 / s->k.resident_cap) & ~size_t(15);
     if (capped > b) b = capped;
   }
   return b;
@@ -228,7 +219,7 @@ size_t lds_bytes(const craft_sim* s, int tile, int obs_bufs = 1, bool pristine =
 void rollout_shape(const craft_sim* s, int* tile, int* threads, int* split) {
   // the rollout kernels stage u8 rows (double-buffered): their default tile keeps ~40 KB per buffer
   const int win = s->cfg.window_width;
-  int t = s->tile_knob ? s->tile_knob : (win == 3 ? 64 : (win == 5 ? 32 : 16)), nt = s->rollout_threads;
+  int t = s->k.tile_knob ? s->k.tile_knob : (win == 3 ? 64 : (win == 5 ? 32 : 16)), nt = s->k.rollout_threads;
   if (nt == 0 && s->cfg.window_width == 3) {
     t = 32;
     nt = 512;
@@ -248,14 +239,14 @@ void rollout_shape(const craft_sim* s, int* tile, int* threads, int* split) {
 // The one-tile teacher kernel's envs per tile: 64 for 3x3 windows; the handle's tile (default 32)
 // for wider ones, whose 64-env observation rows (69 KB at 5x5) leave one workgroup per CU.
 int teach_tile(const craft_sim* s) {
-  return s->cfg.window_width == 3 || s->tile != 32 ? craft::kMaxTileEnvs : 32;
+  return s->cfg.window_width == 3 || s->k.tile != 32 ? craft::kMaxTileEnvs : 32;
 }
 
 // Teacher lanes per env of the one-tile kernel (craft_sim_tune_teach): quads, or pairs on the
 // 32-env tile of wider windows (76.5 against 78.5 us with quads at 5x5), or what the knob says.
 int one_tile_lanes(const craft_sim* s) {
-  return (s->teach_lanes == 1 || s->teach_lanes == 2) ? s->teach_lanes
-         : s->teach_lanes == 0 && teach_tile(s) == 32 ? 2 : 4;
+  return (s->k.teach_lanes == 1 || s->k.teach_lanes == 2) ? s->k.teach_lanes
+         : s->k.teach_lanes == 0 && teach_tile(s) == 32 ? 2 : 4;
 }
 
 // What craft_step / craft_step_ex (teach = false) or craft_step_teach (teach = true) launches:
@@ -264,19 +255,19 @@ int one_tile_lanes(const craft_sim* s) {
 void step_shape(const craft_sim* s, bool teach, int* kernel, int* envs, int* lanes) {
   if (!teach) {
     *kernel = CRAFT_KERNEL_TILE;
-    *envs = s->tile;
+    *envs = s->k.tile;
     *lanes = 0;
     return;
   }
   const bool w3 = s->cfg.window_width == 3;
-  int k = s->teach_kernel;
+  int k = s->k.teach_kernel;
   // auto: the two-tile kernel for 3x3 windows at the default tile from 32768 envs, where its
   // 128-env workgroups fill the chip, else the one-tile kernel
-  if (k == 0) k = (w3 && s->tile == craft::kMaxTileEnvs && s->resident_cap == 0 && s->n_envs >= 32768) ? 2 : 1;
-  if (k == 2 && !(w3 && s->tile == craft::kMaxTileEnvs && s->resident_cap == 0)) k = 1;
+  if (k == 0) k = (w3 && s->k.tile == craft::kMaxTileEnvs && s->k.resident_cap == 0 && s->n_envs >= 32768) ? 2 : 1;
+  if (k == 2 && !(w3 && s->k.tile == craft::kMaxTileEnvs && s->k.resident_cap == 0)) k = 1;
   // teacher lanes per env (craft_sim_tune_teach): the two-tile kernel runs pairs (or quads), the
   // one-tile kernel quads (or pairs, or one lane)
-  const int tl2 = s->teach_lanes == 4 ? 4 : 2;
+  const int tl2 = s->k.teach_lanes == 4 ? 4 : 2;
   const int tl1 = one_tile_lanes(s);
   if (k == 2) { *kernel = 2; *envs = 128; *lanes = tl2; }
   else { *kernel = 1; *envs = teach_tile(s); *lanes = tl1; }
@@ -314,7 +305,7 @@ int flush_table(craft_sim* s, void* stream, const char* what) {
 // The view a teacher launch gets: the table hidden when craft_sim_tune_teach says never.
 SimView teach_view(const craft_sim* s) {
   SimView v = s->view;
-  if (s->teach_table == 2) {
+  if (s->k.teach_table == 2) {
     v.ttab = nullptr;
     v.ttab4 = nullptr;
     v.tt_slots = 0;
@@ -336,7 +327,7 @@ struct TickPlan {
 // kernel takes the view and nw from here and sizes its own LDS.
 int tick_plan(craft_sim* s, bool teach, void* stream, const char* what, TickPlan& p) {
   if (!teach) {
-    p = TickPlan{s->view, 0, 0, s->tile, lds_bytes(s, s->tile)};
+    p = TickPlan{s->view, 0, 0, s->k.tile, lds_bytes(s, s->k.tile)};
     return CRAFT_OK;
   }
   const int rc = flush_table(s, stream, what);
@@ -346,7 +337,7 @@ int tick_plan(craft_sim* s, bool teach, void* stream, const char* what, TickPlan
   // -0.9 us (30.1 -> 29.2) when every launch writes a fresh slot of a 16-slot ring (round 6,
   // profiles/r06/teach_table_k1; round 4's u16 reads cost +0.5 us there), so auto reads it always.
   p.v = teach_view(s);
-  p.v.tt_fused = s->teach_table != 2;
+  p.v.tt_fused = s->k.teach_table != 2;
   p.tl = one_tile_lanes(s);
   p.nw = craft::teach_words(s->view.W, s->view.H);
   p.tile = teach_tile(s);
@@ -358,22 +349,10 @@ int tick_plan(craft_sim* s, bool teach, void* stream, const char* what, TickPlan
 }
 
 int launch(craft_sim* s, int mode, const TileArgs& a, void* stream, const char* what) {
-  hipError_t e = craft::launch_tile(mode, s->cfg.window_width, s->tile, s->view, a, lds_bytes(s, s->tile),
+  hipError_t e = craft::launch_tile(mode, s->cfg.window_width, s->k.tile, s->view, a, lds_bytes(s, s->k.tile),
                                     reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(s, e, what);
   return CRAFT_OK;
-}
-
-// The teachers refuse grids whose BFS would overflow the reference's 1000-state queue.
-int check_bfs_queue(craft_sim* s, const char* what) {
-  if (4 * s->view.C <= 1000) return CRAFT_OK;
-  return fail(s, CRAFT_EINVAL, std::string(what) + ": 4*W*H > 1000 overflows the reference's BFS queue (teachers/base.py:42)");
-}
-
-// Every slot of a rollout's observation ring starts 16-byte aligned (no ring: nothing to check).
-bool ring_slots_aligned(const craft_sim* s, const void* obs, int ring) {
-  const int64_t slot = s->n_envs * (int64_t)s->view.F * craft::obs_elem_bytes(s->view.obs_fmt);
-  return !obs || (aligned16(obs) && (ring <= 1 || slot % 16 == 0));
 }
 
 // The sync area of a rollout launch of a.n_ticks ticks on `st`: a.queue, a.tile_done and the
@@ -496,7 +475,7 @@ int craft_sim_create(const craft_config_t* cfg, int device, int64_t n_envs, int6
   // stats rows: one per 16-env tile, plus the step kernel's last workgroup's tick waves (its
   // wave count is rounded up to the workgroup's 4)
   s->n_tiles = (n_envs + craft::kMinTileEnvs - 1) / craft::kMinTileEnvs + 4;
-  s->tile = default_tile(cfg->window_width);
+  s->k.tile = craft_host::default_tile(cfg->window_width);
   const int W = cfg->width, H = cfg->height, K = cfg->n_kinds, F = cfg->n_features;
   const int C = W * H, CS = (C + 15) & ~15;
   const int GS = CS + 4;                  // odd dword stride: lane-private rows hit distinct banks
@@ -652,16 +631,9 @@ int craft_sim_create(const craft_config_t* cfg, int device, int64_t n_envs, int6
 
 int craft_sim_tune(craft_sim_t* s, int32_t tile_envs, int32_t max_resident_per_cu, int32_t obs_store) {
   if (!s) return CRAFT_EINVAL;
-  s->tile_knob = tile_envs;
-  if (tile_envs == 0) tile_envs = default_tile(s->cfg.window_width);
-  if (tile_envs != 16 && tile_envs != 32 && tile_envs != 64)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune: tile_envs must be 16, 32 or 64");
-  if (max_resident_per_cu != 0 && (max_resident_per_cu < 3 || max_resident_per_cu > 32))
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune: max_resident_per_cu must be 0 or 3..32");
-  if (obs_store < 0 || obs_store > 2)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune: obs_store must be 0 (write-back), 1 (nontemporal) or 2 (write-through)");
-  s->tile = tile_envs;
-  s->resident_cap = max_resident_per_cu;
+  if (const int rc = craft_host::set_tune(s->k, s->cfg.window_width, tile_envs, max_resident_per_cu, obs_store,
+                                          s->last_error))
+    return rc;
   s->view.obs_policy = obs_store;
   s->rollout_obs_policy = obs_store;
   s->obs_store_tuned = true;
@@ -670,25 +642,14 @@ int craft_sim_tune(craft_sim_t* s, int32_t tile_envs, int32_t max_resident_per_c
 
 int craft_sim_tune_teach(craft_sim_t* s, int32_t kernel, int32_t lanes, int32_t table) {
   if (!s) return CRAFT_EINVAL;
-  if (kernel < 0 || kernel > 2)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_teach: kernel must be 0 (auto), 1 (one-tile) or 2 (two-tile)");
-  if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_teach: lanes must be 0 (default), 1, 2 or 4");
-  if (table < 0 || table > 2)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_teach: table must be 0 (auto), 1 (always) or 2 (never)");
-  s->teach_kernel = kernel;
-  s->teach_lanes = lanes;
-  s->teach_table = table;
-  return CRAFT_OK;
+  return craft_host::set_tune_teach(s->k, kernel, lanes, table, s->last_error);
 }
 
 int craft_abi_version(void) { return CRAFT_ABI_VERSION; }
 
 int craft_sim_tune_host(craft_sim_t* s, int32_t threads) {
   if (!s) return CRAFT_EINVAL;
-  if (threads < 0 || threads > 1024)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_host: threads must be 0 (the machine's) or 1..1024");
-  return CRAFT_OK;                          // (no host workers in this library)
+  return craft_host::check_tune_host(threads, s->last_error);   // (no host workers in this library)
 }
 
 int craft_sim_sync_table(craft_sim_t* s, void* stream) {
@@ -709,19 +670,12 @@ int craft_sim_step_shape(const craft_sim_t* s, int32_t teach, int32_t* kernel, i
 
 int craft_sim_tune_rollout(craft_sim_t* s, int32_t chunk_ticks, int32_t threads) {
   if (!s) return CRAFT_EINVAL;
-  if (chunk_ticks < -1 || chunk_ticks > 4096)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_rollout: chunk_ticks must be -1..4096");
-  if (threads != 0 && threads != 128 && threads != 256 && threads != 320 && threads != 384 && threads != 512)
-    return fail(s, CRAFT_EINVAL, "craft_sim_tune_rollout: threads must be 0, 128, 256, 320, 384 or 512");
-  s->rollout_chunk = chunk_ticks;
-  s->rollout_threads = threads;
-  return CRAFT_OK;
+  return craft_host::set_tune_rollout(s->k, chunk_ticks, threads, s->last_error);
 }
 
 int craft_sim_set_obs_format(craft_sim_t* s, int32_t format) {
   if (!s) return CRAFT_EINVAL;
-  if (format != CRAFT_OBS_F32 && format != CRAFT_OBS_BF16 && format != CRAFT_OBS_U8)
-    return fail(s, CRAFT_EINVAL, "craft_sim_set_obs_format: format must be 0 (fp32), 1 (bf16) or 2 (u8)");
+  if (const int rc = craft_host::set_obs_format(s->k, format, s->last_error)) return rc;
   s->view.obs_fmt = format;
   return CRAFT_OK;
 }
@@ -777,7 +731,7 @@ int craft_sim_rollout_shape(const craft_sim_t* s, int32_t* tile_envs, int32_t* t
 
 int craft_sim_tile_shape(const craft_sim_t* s, int32_t* tile_envs, int32_t* obs_store) {
   if (!s) return CRAFT_EINVAL;
-  if (tile_envs) *tile_envs = s->tile;
+  if (tile_envs) *tile_envs = s->k.tile;
   if (obs_store) *obs_store = s->view.obs_policy;
   return CRAFT_OK;
 }
@@ -807,8 +761,8 @@ int craft_sim_error_word(craft_sim_t* s, int32_t* out, void* stream) {
 }
 
 int craft_pool_load(craft_sim_t* s, const uint8_t* grids, int32_t first, int32_t count) {
-  if (!s || !grids || first < 0 || count < 0) return fail(s, CRAFT_EINVAL, "craft_pool_load: bad argument");
-  if ((int64_t)first + count > s->pool_capacity) return fail(s, CRAFT_ERANGE, "craft_pool_load: beyond pool capacity");
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_pool_load(facts(s), grids, first, count, s->last_error)) return rc;
   const int C = s->cfg.width * s->cfg.height, CS = s->view.CS;
   std::vector<uint8_t> staged((size_t)count * CS, 0);
   std::vector<uint8_t> conn((size_t)count, 0);
@@ -841,19 +795,11 @@ int craft_pool_generate(craft_sim_t* s, uint64_t seed, int64_t scenario_id0, int
                         int32_t boundary_kind, const int32_t* primitives, int32_t n_primitive_kinds,
                         int32_t n_per_primitive, const int32_t* workshop_kind, int32_t n_workshops,
                         int32_t* init_pos_out, void* stream) {
-  if (!s || first < 0 || count < 0 || n_primitive_kinds < 0 || n_primitive_kinds > 8 || n_per_primitive < 0 ||
-      n_workshops < 0 || n_workshops > 8 || (n_primitive_kinds && !primitives) || (n_workshops && !workshop_kind))
-    return fail(s, CRAFT_EINVAL, "craft_pool_generate: bad argument");
-  if ((int64_t)first + count > s->pool_capacity) return fail(s, CRAFT_ERANGE, "craft_pool_generate: beyond pool capacity");
-  const int K = s->cfg.n_kinds, W = s->cfg.width, H = s->cfg.height;
-  auto bad_kind = [&](int k) { return k <= 0 || k >= K; };
-  if (bad_kind(boundary_kind)) return fail(s, CRAFT_EINVAL, "craft_pool_generate: bad boundary kind");
-  for (int i = 0; i < n_primitive_kinds; ++i)
-    if (bad_kind(primitives[i])) return fail(s, CRAFT_EINVAL, "craft_pool_generate: bad primitive kind");
-  for (int i = 0; i < n_workshops; ++i)
-    if (bad_kind(workshop_kind[i])) return fail(s, CRAFT_EINVAL, "craft_pool_generate: bad workshop kind");
-  if ((int64_t)n_primitive_kinds * n_per_primitive + n_workshops + 1 > (int64_t)(W - 2) * (H - 2))
-    return fail(s, CRAFT_EINVAL, "craft_pool_generate: more objects than interior cells");
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_pool_generate(facts(s), first, count, boundary_kind, primitives,
+                                                     n_primitive_kinds, n_per_primitive, workshop_kind, n_workshops,
+                                                     s->last_error))
+    return rc;
   craft::ScenarioArgs a{};
   a.seed = seed;
   a.id0 = scenario_id0;
@@ -891,8 +837,8 @@ int craft_pool_generate(craft_sim_t* s, uint64_t seed, int64_t scenario_id0, int
 
 int craft_reset(craft_sim_t* s, const int32_t* scenario, const int32_t* pos_x, const int32_t* pos_y,
                 const int32_t* dir, const int32_t* task, void* obs, void* stream) {
-  if (!s || !scenario || !pos_x || !pos_y || !dir || !task) return fail(s, CRAFT_EINVAL, "craft_reset: null input");
-  if (obs && !aligned16(obs)) return fail(s, CRAFT_EINVAL, "craft_reset: obs must be 16-byte aligned");
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_reset(scenario, pos_x, pos_y, dir, task, obs, s->last_error)) return rc;
   TileArgs a{};
   a.r_scen = scenario; a.r_x = pos_x; a.r_y = pos_y; a.r_dir = dir; a.r_task = task;
   a.n = s->n_envs;
@@ -918,11 +864,9 @@ int craft_step(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, int
 }
 
 namespace {
-int step_args(craft_sim_t* s, const craft_step_args_t* x, TileArgs& a) {
-  if (x->obs && !aligned16(x->obs)) return fail(s, CRAFT_EINVAL, "craft_step: obs must be 16-byte aligned");
-  if (x->behavior_clone && !x->ref_actions)
-    return fail(s, CRAFT_EINVAL, "craft_step_ex: behavior_clone needs ref_actions");
-  a = TileArgs{};
+// The tile kernel's arguments of a (checked) craft_step_args_t.
+TileArgs step_args(const craft_sim_t* s, const craft_step_args_t* x) {
+  TileArgs a{};
   a.actions = x->actions;
   a.seed = x->action_seed;
   a.tick = x->tick;
@@ -937,17 +881,15 @@ int step_args(craft_sim_t* s, const craft_step_args_t* x, TileArgs& a) {
   a.rec = x->action_record;
   a.any_live = x->any_live;
   a.code = x->transition_code;
-  return CRAFT_OK;
+  return a;
 }
 }  // namespace
 
 int craft_step_teach(craft_sim_t* s, const craft_step_args_t* x, int32_t* label_out, void* stream) {
   if (!s || !x || !label_out) return CRAFT_EINVAL;
-  int rc = check_bfs_queue(s, "craft_step_teach");
+  int rc = craft_host::check_step_teach(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
-  TileArgs a;
-  rc = step_args(s, x, a);
-  if (rc != CRAFT_OK) return rc;
+  TileArgs a = step_args(s, x);
   a.label = label_out;
   int kernel = 0, envs = 0, tl = 0;
   step_shape(s, true, &kernel, &envs, &tl);
@@ -964,10 +906,7 @@ int craft_step_teach(craft_sim_t* s, const craft_step_args_t* x, int32_t* label_
 
 int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* stream) {
   if (!s || !x) return CRAFT_EINVAL;
-  if (x->flags != 0) return fail(s, CRAFT_EINVAL, "craft_step_lang: flags must be 0 (no auto-reset in this protocol)");
-  if (x->use_alt && !x->alt_actions) return fail(s, CRAFT_EINVAL, "craft_step_lang: use_alt needs alt_actions");
-  if (x->obs && !aligned16(x->obs)) return fail(s, CRAFT_EINVAL, "craft_step_lang: obs must be 16-byte aligned");
-  int rc = x->label_out ? check_bfs_queue(s, "craft_step_lang") : CRAFT_OK;
+  int rc = craft_host::check_step_lang(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
   TileArgs a{};
   a.actions = x->actions;
@@ -995,8 +934,7 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* strea
 
 int craft_episode_queue(craft_sim_t* s, const int32_t* specs, int64_t count) {
   if (!s) return CRAFT_EINVAL;
-  if (!specs || count < 1 || count > (int64_t)INT32_MAX)
-    return fail(s, CRAFT_EINVAL, "craft_episode_queue: specs must hold 1 .. 2^31 - 1 entries");
+  if (const int rc = craft_host::check_episode_queue(specs, count, s->last_error)) return rc;
   HIP_TRY(s, hipSetDevice(s->device));
   // the handle's own buffers, once: the cursors, craft_episode_begin's reset inputs, the check's word
   if (!s->d_cursor) {
@@ -1031,8 +969,7 @@ int craft_episode_queue(craft_sim_t* s, const int32_t* specs, int64_t count) {
   }
   if (bad != ~0ull) {
     (void)hipFree(q);                        // the queue installed before stays in force
-    return fail(s, CRAFT_EINVAL, "craft_episode_queue: entry " + std::to_string(bad) +
-                                     " is invalid (scenario, position, direction or task out of range)");
+    return craft_host::queue_entry_invalid(bad, s->last_error);
   }
   // ticks of the old queue may still be running on some stream: they finish first
   HIP_TRY(s, hipDeviceSynchronize());
@@ -1045,19 +982,9 @@ int craft_episode_queue(craft_sim_t* s, const int32_t* specs, int64_t count) {
 
 int craft_episode_begin(craft_sim_t* s, int64_t first, int64_t stride, uint32_t flags, void* obs, void* stream) {
   if (!s) return CRAFT_EINVAL;
-  if (!s->d_queue) return fail(s, CRAFT_EINVAL, "craft_episode_begin: no episode queue installed (craft_episode_queue)");
-  if (stride < 1) return fail(s, CRAFT_EINVAL, "craft_episode_begin: stride must be >= 1");
-  if (first < 0) return fail(s, CRAFT_EINVAL, "craft_episode_begin: first must be >= 0");
-  if (flags & ~CRAFT_QUEUE_WRAP) return fail(s, CRAFT_EINVAL, "craft_episode_begin: unknown flag");
-  if (obs && !aligned16(obs)) return fail(s, CRAFT_EINVAL, "craft_episode_begin: obs must be 16-byte aligned");
+  if (const int rc = craft_host::check_episode_begin(facts(s), first, stride, flags, obs, s->last_error)) return rc;
   const bool wrap = (flags & CRAFT_QUEUE_WRAP) != 0;
-  const int64_t count = s->q_count;
-  if (first > INT64_MAX - s->env_base - s->n_envs)
-    return fail(s, CRAFT_EINVAL, "craft_episode_begin: first is out of range");
-  const int64_t g0 = first + s->env_base;
-  if (!wrap && s->n_envs > 0 && g0 + s->n_envs - 1 >= count)
-    return fail(s, CRAFT_EINVAL, "craft_episode_begin: slot " + std::to_string(std::max<int64_t>(count - g0, 0)) +
-                                     " would start past the end of the queue (" + std::to_string(count) + " entries)");
+  const int64_t count = s->q_count, g0 = first + s->env_base;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const hipError_t e = craft::launch_queue_begin(s->d_queue, count, g0, wrap ? 1 : 0, s->n_envs, s->d_cursor,
                                                  s->d_qreset, st);
@@ -1074,15 +1001,9 @@ int craft_episode_begin(craft_sim_t* s, int64_t first, int64_t stride, uint32_t 
 
 int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* stream) {
   if (!s || !x) return CRAFT_EINVAL;
-  if (x->step.flags != CRAFT_STEP_AUTORESET)
-    return fail(s, CRAFT_EINVAL, "craft_step_stream: step.flags must be CRAFT_STEP_AUTORESET");
-  if (!s->d_queue || !s->q_begun)
-    return fail(s, CRAFT_EINVAL, "craft_step_stream: craft_episode_begin has not put the slots on the queue");
-  int rc = x->label_out ? check_bfs_queue(s, "craft_step_stream") : CRAFT_OK;
+  int rc = craft_host::check_step_stream(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
-  TileArgs a;
-  rc = step_args(s, &x->step, a);
-  if (rc != CRAFT_OK) return rc;
+  TileArgs a = step_args(s, &x->step);
   a.label = x->label_out;
   a.q_entries = s->d_queue;
   a.q_cursor = s->d_cursor;
@@ -1103,20 +1024,15 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* s
 
 int craft_step_ex(craft_sim_t* s, const craft_step_args_t* x, void* stream) {
   if (!s || !x) return CRAFT_EINVAL;
-  TileArgs a;
-  const int rc = step_args(s, x, a);
-  if (rc != CRAFT_OK) return rc;
-  return launch(s, craft::MODE_TICK, a, stream, "craft_step launch");
+  if (const int rc = craft_host::check_step(x, s->last_error)) return rc;
+  return launch(s, craft::MODE_TICK, step_args(s, x), stream, "craft_step launch");
 }
 
 int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, int64_t tick0,
                   int32_t n_ticks, uint32_t flags, void* obs, int32_t ring, float* reward,
                   uint8_t* done, int8_t* success, void* stream) {
   if (!s) return CRAFT_EINVAL;
-  if (n_ticks < 0 || ring < 1 || tick0 < 0)
-    return fail(s, CRAFT_EINVAL, "craft_rollout: need n_ticks >= 0, ring >= 1, tick0 >= 0");
-  if (!ring_slots_aligned(s, obs, ring))
-    return fail(s, CRAFT_EINVAL, "craft_rollout: every obs ring slot must be 16-byte aligned");
+  if (const int rc = craft_host::check_rollout(facts(s), tick0, n_ticks, ring, obs, s->last_error)) return rc;
   craft::RolloutArgs a{};
   a.actions = actions;
   a.seed = action_seed;
@@ -1128,13 +1044,13 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
   a.reward = reward;
   a.done = done;
   a.sat = success;
-  a.chunk = s->rollout_chunk > 0 ? s->rollout_chunk : (n_ticks > 0 ? n_ticks : 1);
+  a.chunk = s->k.rollout_chunk > 0 ? s->k.rollout_chunk : (n_ticks > 0 ? n_ticks : 1);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int tile = 0, threads = 0, split = 0;
   rollout_shape(s, &tile, &threads, &split);
   // chunk_ticks -1: the split kernel's continuous pipeline (its 3x3 default shape, observations
   // on; otherwise one unit per tile)
-  const bool flat = s->rollout_chunk == -1 && split && tile == 32 && threads == 512 &&
+  const bool flat = s->k.rollout_chunk == -1 && split && tile == 32 && threads == 512 &&
                     s->cfg.window_width == 3 && obs != nullptr;
   a.flat = flat ? 1 : 0;
   // Chunked launches (tiles handed between workgroups) need zeroed per-tile flags.
@@ -1159,16 +1075,10 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
 
 int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, void* stream) {
   if (!s || !x) return CRAFT_EINVAL;
-  if (x->n_ticks < 0 || x->ring < 1 || x->tick0 < 0)
-    return fail(s, CRAFT_EINVAL, "craft_rollout_teach: need n_ticks >= 0, ring >= 1, tick0 >= 0");
-  int rc = check_bfs_queue(s, "craft_rollout_teach");
+  int rc = craft_host::check_rollout_teach(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
-  const bool lsync = x->label_actions != 0 || x->behavior_clone != nullptr;
-  if (lsync && !x->label_in)
-    return fail(s, CRAFT_EINVAL, "craft_rollout_teach: label_actions / behavior_clone need label_in");
-  if (!ring_slots_aligned(s, x->obs, x->ring))
-    return fail(s, CRAFT_EINVAL, "craft_rollout_teach: every obs ring slot must be 16-byte aligned");
   if (x->n_ticks == 0) return CRAFT_OK;
+  const bool lsync = x->label_actions != 0 || x->behavior_clone != nullptr;
   craft::RolloutArgs a{};
   a.actions = x->actions;
   a.seed = x->action_seed;
@@ -1187,7 +1097,7 @@ int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, voi
   // 2: the transition wave looks labels up itself and waits only for BFS answers; 1: it waits
   // for each item's whole row (a task without a hint table: the walk stays with the teacher)
   a.lsync = lsync ? (s->hint_walk ? 1 : 2) : 0;
-  a.use_table = s->teach_table != 2;              // auto = always: the reads overlap the stream
+  a.use_table = s->k.teach_table != 2;              // auto = always: the reads overlap the stream
   a.labels = x->labels;
   a.rec = x->action_record;
   rc = flush_table(s, stream, "craft_rollout_teach");
@@ -1224,8 +1134,7 @@ int craft_transition(craft_sim_t* s, const int32_t* src, const int32_t* dst, con
                      int64_t n, int8_t* code_out, void* stream) {
   if (!s) return CRAFT_EINVAL;
   if (n == 0) return CRAFT_OK;
-  if (!actions || n < 0) return fail(s, CRAFT_EINVAL, "craft_transition: bad argument");
-  if (!src && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_transition: n > n_envs");
+  if (const int rc = craft_host::check_transition(facts(s), src, actions, n, s->last_error)) return rc;
   TileArgs a{};
   a.src = src;
   a.dst = dst;
@@ -1239,9 +1148,7 @@ int craft_observe(craft_sim_t* s, const int32_t* slots, int64_t n, const int32_t
                   int8_t* sat, void* stream) {
   if (!s) return CRAFT_EINVAL;
   if (n == 0) return CRAFT_OK;
-  if (n < 0) return fail(s, CRAFT_EINVAL, "craft_observe: bad argument");
-  if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_observe: n > n_envs");
-  if (obs && !aligned16(obs)) return fail(s, CRAFT_EINVAL, "craft_observe: obs must be 16-byte aligned");
+  if (const int rc = craft_host::check_observe(facts(s), slots, n, obs, s->last_error)) return rc;
   TileArgs a{};
   a.src = slots;
   a.tasks = tasks;
@@ -1255,10 +1162,8 @@ int craft_rollout_distances(craft_sim_t* s, const int32_t* tasks, const int8_t* 
                             const int32_t* action_seqs, int32_t ticks, int32_t* distances_out,
                             uint8_t* is_get_out, int32_t* n_actions_out, int32_t* flags_out, void* stream) {
   if (!s) return CRAFT_EINVAL;
-  if (!tasks || !success || !distances_out || !is_get_out || !n_actions_out || !flags_out || ticks < 0 ||
-      (ticks > 0 && !action_seqs))
-    return fail(s, CRAFT_EINVAL, "craft_rollout_distances: bad argument");
-  int rc = check_bfs_queue(s, "craft_rollout_distances");
+  int rc = craft_host::check_rollout_distances(facts(s), tasks, success, action_seqs, ticks, distances_out, is_get_out,
+                                               n_actions_out, flags_out, s->last_error);
   if (rc != CRAFT_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   HIP_TRY(s, hipMemsetAsync(flags_out, 0, 2 * sizeof(int32_t), st));
@@ -1275,13 +1180,11 @@ int craft_teacher(craft_sim_t* s, const int32_t* slots, int64_t n, const int32_t
                   int32_t* path_len_out, void* stream) {
   if (!s) return CRAFT_EINVAL;
   if (n == 0) return CRAFT_OK;
-  if (!action_out || n < 0) return fail(s, CRAFT_EINVAL, "craft_teacher: bad argument");
-  if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_teacher: n > n_envs");
-  int rc = check_bfs_queue(s, "craft_teacher");
+  int rc = craft_host::check_teacher(facts(s), slots, n, action_out, s->last_error);
   if (rc != CRAFT_OK) return rc;
   rc = flush_table(s, stream, "craft_teacher");
   if (rc != CRAFT_OK) return rc;
-  hipError_t e = craft::launch_teacher(craft::teach_words(s->view.W, s->view.H), s->teach_lanes, teach_view(s), slots, tasks, n, action_out,
+  hipError_t e = craft::launch_teacher(craft::teach_words(s->view.W, s->view.H), s->k.teach_lanes, teach_view(s), slots, tasks, n, action_out,
                                        path_len_out, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(s, e, "craft_teacher launch");
   return CRAFT_OK;
@@ -1291,8 +1194,7 @@ int craft_get_state(craft_sim_t* s, const int32_t* slots, int64_t n, int32_t* ag
                     uint8_t* grid, int32_t* spec, void* stream) {
   if (!s) return CRAFT_EINVAL;
   if (n == 0) return CRAFT_OK;
-  if (n < 0) return fail(s, CRAFT_EINVAL, "craft_get_state: bad argument");
-  if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_get_state: n > n_envs");
+  if (const int rc = craft_host::check_get_state(facts(s), slots, n, s->last_error)) return rc;
   hipLaunchKernelGGL(craft::get_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), s->view, slots, n, agent, inventory, grid, spec);
   hipError_t e = hipGetLastError();
@@ -1304,8 +1206,7 @@ int craft_set_state(craft_sim_t* s, const int32_t* slots, int64_t n, const int32
                     const int32_t* inventory, void* stream) {
   if (!s) return CRAFT_EINVAL;
   if (n == 0) return CRAFT_OK;
-  if (n < 0 || !spec || !agent) return fail(s, CRAFT_EINVAL, "craft_set_state: bad argument");
-  if (!slots && n > s->n_envs) return fail(s, CRAFT_ERANGE, "craft_set_state: n > n_envs");
+  if (const int rc = craft_host::check_set_state(facts(s), slots, n, spec, agent, s->last_error)) return rc;
   hipLaunchKernelGGL(craft::set_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), s->view, slots, n, spec, agent, inventory);
   hipError_t e = hipGetLastError();

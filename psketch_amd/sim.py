@@ -30,6 +30,28 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _put(struct, keep, field, t):
+    """Points struct.field at tensor t, which `keep` holds alive until the call returns (None:
+    the field stays null)."""
+    if t is not None:
+        keep.append(t)
+        setattr(struct, field, t.data_ptr())
+
+
+def _ring_extent(named_outputs, n):
+    """The ring length R the given [R, N, ...] outputs of a multi-tick launch share (None: no
+    output given)."""
+    ring = None
+    for name, t in named_outputs:
+        if t is not None:
+            if t.dim() < 1 or t.shape[0] < 1:
+                raise ValueError(f"{name} must be a ring [R >= 1, {n}, ...]")
+            if ring is not None and t.shape[0] != ring:
+                raise ValueError(f"{name} ring {t.shape[0]} != ring {ring} of the other outputs")
+            ring = t.shape[0]
+    return ring
+
+
 class CraftSim:
     """N CraftWorld environments on one GPU.
 
@@ -219,6 +241,36 @@ class CraftSim:
             raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
         return t
 
+    def _put_bufs(self, struct, keep, table):
+        """_buf, then _put, for every (field, tensor, dtype, shape) row: the struct's field
+        carries the argument's name."""
+        for field, t, dtype, shape in table:
+            _put(struct, keep, field, self._buf(field, t, dtype, shape))
+
+    def _flag_mask(self, name, x, n):
+        """A per-slot flag argument as the uint8 [n] device tensor the ABI takes."""
+        m = torch.as_tensor(x, device=self.device)
+        m = (m != 0).to(torch.uint8).contiguous() if m.dtype != torch.uint8 else m.contiguous()
+        if m.numel() != n:
+            raise ValueError(f"{name}: expected {n} entries")
+        return m
+
+    def _step_fields(self, st, keep, actions, ref_actions, behavior_clone, obs, reward, done, success,
+                     action_record, any_live, transition_code):
+        """The pointer fields of a craft_step_args_t (step, step_stream)."""
+        n = self.n_envs
+        _put(st, keep, "actions", self._i32(actions, n) if actions is not None else None)
+        _put(st, keep, "ref_actions", self._i32(ref_actions, n) if ref_actions is not None else None)
+        if behavior_clone is not None:
+            _put(st, keep, "behavior_clone", self._flag_mask("behavior_clone", behavior_clone, n))
+        self._put_bufs(st, keep, (("reward", reward, torch.float32, (n,)),
+                                  ("done", done, torch.uint8, (n,)),
+                                  ("success", success, torch.int8, (n,)),
+                                  ("action_record", action_record, torch.int32, (n,)),
+                                  ("any_live", any_live, torch.int32, (1,)),
+                                  ("transition_code", transition_code, torch.int8, (n,)),
+                                  ("obs", obs, self.obs_dtype, (n, self.n_features))))
+
     def empty_obs(self, n=None):
         n = self.n_envs if n is None else n
         return torch.empty((n, self.n_features), dtype=self.obs_dtype, device=self.device)
@@ -298,29 +350,8 @@ class CraftSim:
             return obs
         args = N.craft_step_args_t()
         keep = []
-
-        def put(field, t):
-            if t is not None:
-                keep.append(t)
-                setattr(args, field, t.data_ptr())
-
-        put("actions", self._i32(actions, n) if actions is not None else None)
-        put("ref_actions", self._i32(ref_actions, n) if ref_actions is not None else None)
-        if behavior_clone is not None:
-            bc = torch.as_tensor(behavior_clone, device=self.device)
-            bc = (bc != 0).to(torch.uint8).contiguous() if bc.dtype != torch.uint8 else bc.contiguous()
-            if bc.numel() != n:
-                raise ValueError(f"behavior_clone: expected {n} entries")
-            put("behavior_clone", bc)
-        for name, t, dt, shape in (("reward", reward, torch.float32, (n,)),
-                                   ("done", done, torch.uint8, (n,)),
-                                   ("success", success, torch.int8, (n,)),
-                                   ("action_record", action_record, torch.int32, (n,)),
-                                   ("any_live", any_live, torch.int32, (1,)),
-                                   ("transition_code", transition_code, torch.int8, (n,))):
-            put(name, self._buf(name, t, dt, shape))
-        self._obs(obs)
-        put("obs", obs)
+        self._step_fields(args, keep, actions, ref_actions, behavior_clone, obs, reward, done, success,
+                          action_record, any_live, transition_code)
         args.action_seed = seed & (2**64 - 1)
         args.tick = int(tick)
         args.flags = flags
@@ -347,30 +378,18 @@ class CraftSim:
         n = self.n_envs
         args = N.craft_lang_step_args_t()
         keep = []
-
-        def put(field, t):
-            if t is not None:
-                keep.append(t)
-                setattr(args, field, t.data_ptr())
-
-        put("actions", self._i32(actions, n) if actions is not None else None)
-        put("alt_actions", self._i32(alt_actions, n) if alt_actions is not None else None)
+        _put(args, keep, "actions", self._i32(actions, n) if actions is not None else None)
+        _put(args, keep, "alt_actions", self._i32(alt_actions, n) if alt_actions is not None else None)
         if use_alt is not None:
-            ua = torch.as_tensor(use_alt, device=self.device)
-            ua = (ua != 0).to(torch.uint8).contiguous() if ua.dtype != torch.uint8 else ua.contiguous()
-            if ua.numel() != n:
-                raise ValueError(f"use_alt: expected {n} entries")
-            put("use_alt", ua)
-        for name, t, dt, shape in (("done", done, torch.uint8, (n,)),
-                                   ("success", success, torch.int8, (n,)),
-                                   ("action_record", action_record, torch.int32, (n,)),
-                                   ("ask_record", ask_record, torch.int8, (n,)),
-                                   ("transition_code", transition_code, torch.int8, (n,)),
-                                   ("any_live", any_live, torch.int32, (1,)),
-                                   ("label_out", labels, torch.int32, (n,))):
-            put(name, self._buf(name, t, dt, shape))
-        self._obs(obs)
-        put("obs", obs)
+            _put(args, keep, "use_alt", self._flag_mask("use_alt", use_alt, n))
+        self._put_bufs(args, keep, (("done", done, torch.uint8, (n,)),
+                                    ("success", success, torch.int8, (n,)),
+                                    ("action_record", action_record, torch.int32, (n,)),
+                                    ("ask_record", ask_record, torch.int8, (n,)),
+                                    ("transition_code", transition_code, torch.int8, (n,)),
+                                    ("any_live", any_live, torch.int32, (1,)),
+                                    ("label_out", labels, torch.int32, (n,)),
+                                    ("obs", obs, self.obs_dtype, (n, self.n_features))))
         args.action_seed = seed & (2**64 - 1)
         args.tick = int(tick)
         args.flags = int(flags)
@@ -418,36 +437,15 @@ class CraftSim:
         n = self.n_envs
         args = N.craft_stream_step_args_t()
         keep = []
-
-        def put(struct, field, t):
-            if t is not None:
-                keep.append(t)
-                setattr(struct, field, t.data_ptr())
-
         st = args.step
-        put(st, "actions", self._i32(actions, n) if actions is not None else None)
-        put(st, "ref_actions", self._i32(ref_actions, n) if ref_actions is not None else None)
-        if behavior_clone is not None:
-            bc = torch.as_tensor(behavior_clone, device=self.device)
-            bc = (bc != 0).to(torch.uint8).contiguous() if bc.dtype != torch.uint8 else bc.contiguous()
-            if bc.numel() != n:
-                raise ValueError(f"behavior_clone: expected {n} entries")
-            put(st, "behavior_clone", bc)
-        for name, t, dt, shape in (("reward", reward, torch.float32, (n,)),
-                                   ("done", done, torch.uint8, (n,)),
-                                   ("success", success, torch.int8, (n,)),
-                                   ("action_record", action_record, torch.int32, (n,)),
-                                   ("any_live", any_live, torch.int32, (1,)),
-                                   ("transition_code", transition_code, torch.int8, (n,))):
-            put(st, name, self._buf(name, t, dt, shape))
-        self._obs(obs)
-        put(st, "obs", obs)
+        self._step_fields(st, keep, actions, ref_actions, behavior_clone, obs, reward, done, success,
+                          action_record, any_live, transition_code)
         st.action_seed = seed & (2**64 - 1)
         st.tick = int(tick)
         st.flags = N.STEP_AUTORESET
-        for name, t in (("label_out", labels), ("episode_end", episode_end),
-                        ("end_pose", end_pose), ("episode_now", episode_now)):
-            put(args, name, self._buf(name, t, torch.int32, (n,)))
+        self._put_bufs(args, keep, [(name, t, torch.int32, (n,)) for name, t in (
+            ("label_out", labels), ("episode_end", episode_end), ("end_pose", end_pose),
+            ("episode_now", episode_now))])
         self._check(self._L.craft_step_stream(self._h, ctypes.byref(args), self._stream()),
                     "craft_step_stream")
         return obs
@@ -473,14 +471,7 @@ class CraftSim:
                                              N.STEP_AUTORESET if autoreset else 0, *c[2],
                                              self._stream()), "craft_rollout")
                 return obs
-        ring = None
-        for name, t in (("obs", obs), ("reward", reward), ("done", done), ("success", success)):
-            if t is not None:
-                if t.dim() < 1 or t.shape[0] < 1:
-                    raise ValueError(f"{name} must be a ring [R >= 1, {n}, ...]")
-                if ring is not None and t.shape[0] != ring:
-                    raise ValueError(f"{name} ring {t.shape[0]} != ring {ring} of the other outputs")
-                ring = t.shape[0]
+        ring = _ring_extent((("obs", obs), ("reward", reward), ("done", done), ("success", success)), n)
         if obs is not None:
             self._buf("obs", obs, self.obs_dtype, (ring, n, self.n_features))
         for name, t, dt in (("reward", reward, torch.float32), ("done", done, torch.uint8),
@@ -533,41 +524,20 @@ class CraftSim:
                 return labels
         args = N.craft_rollout_teach_args_t()
         keep = []
-
-        def put(field, t):
-            if t is not None:
-                keep.append(t)
-                setattr(args, field, t.data_ptr())
-
-        ring = None
-        outs = (("obs", obs), ("reward", reward), ("done", done), ("success", success),
-                ("labels", labels), ("action_record", action_record))
-        for name, t in outs:
-            if t is not None:
-                if t.dim() < 1 or t.shape[0] < 1:
-                    raise ValueError(f"{name} must be a ring [R >= 1, {n}, ...]")
-                if ring is not None and t.shape[0] != ring:
-                    raise ValueError(f"{name} ring {t.shape[0]} != ring {ring} of the other outputs")
-                ring = t.shape[0]
-        ring = ring or 1
-        if obs is not None:
-            self._buf("obs", obs, self.obs_dtype, (ring, n, self.n_features))
-        for name, t, dt in (("reward", reward, torch.float32), ("done", done, torch.uint8),
-                            ("success", success, torch.int8), ("labels", labels, torch.int32),
-                            ("action_record", action_record, torch.int32)):
-            self._buf(name, t, dt, (ring, n) if t is not None else ())
-        for name, t in outs:
-            put(name, t)
+        ring = _ring_extent((("obs", obs), ("reward", reward), ("done", done), ("success", success),
+                             ("labels", labels), ("action_record", action_record)), n) or 1
+        self._put_bufs(args, keep, (("obs", obs, self.obs_dtype, (ring, n, self.n_features)),
+                                    ("reward", reward, torch.float32, (ring, n)),
+                                    ("done", done, torch.uint8, (ring, n)),
+                                    ("success", success, torch.int8, (ring, n)),
+                                    ("labels", labels, torch.int32, (ring, n)),
+                                    ("action_record", action_record, torch.int32, (ring, n))))
         if actions is not None:
-            put("actions", self._i32(actions, n * n_ticks))
+            _put(args, keep, "actions", self._i32(actions, n * n_ticks))
         if label_in is not None:
-            put("label_in", self._i32(label_in, n))
+            _put(args, keep, "label_in", self._i32(label_in, n))
         if behavior_clone is not None:
-            bc = torch.as_tensor(behavior_clone, device=self.device)
-            bc = (bc != 0).to(torch.uint8).contiguous() if bc.dtype != torch.uint8 else bc.contiguous()
-            if bc.numel() != n:
-                raise ValueError(f"behavior_clone: expected {n} entries")
-            put("behavior_clone", bc)
+            _put(args, keep, "behavior_clone", self._flag_mask("behavior_clone", behavior_clone, n))
         args.label_actions = 1 if label_actions else 0
         args.action_seed = seed & (2**64 - 1)
         args.tick0 = int(tick0)
