@@ -456,6 +456,50 @@ typedef struct {
 } craft_stream_step_args_t;
 int craft_step_stream(craft_sim_t* sim, const craft_stream_step_args_t* args, void* stream);
 
+/* craft_step_lang on the episode queue: the language trainers' tick (step first, then the timer,
+ * success read off the state the step left) whose finished slots restart on their next queue
+ * entry.  It is what the three language trainers' inherited evaluate (trainers/imitation.py:
+ * 183-226 over their own do_rollout) and an endless stream of fresh episodes for a language
+ * student (CRAFT_QUEUE_WRAP) sit on.  Against craft_step_stream's protocol an episode that times
+ * out takes max_timesteps steps, not one fewer; the ending tick moves, grabs or crafts like any
+ * other; and end_pose is the pose AFTER that step.  Per slot, in this order:
+ *   a slot frozen before the tick takes no step and leaves no record: action_record, ask_record
+ *     and transition_code -1, done 1, success = satisfies() of its final state, label -1,
+ *     episode_end, end_pose and episode_now -1;
+ *   a = use_alt[i] ? alt_actions[i] : actions[i]; an a outside 0..5 latches CRAFT_EBADACTION and
+ *     the slot stays as it is: no step, no timer drop, no episode end, no restart, its cursor
+ *     untouched (done 0, success -1, episode_now its cursor);
+ *   state = step(state, a); timer -= 1; ended = (a == STOP) or timer <= 0; the records are the
+ *     action, the ask bit and the transition code of that step, on the ending tick too;
+ *   ended: done 1, success = satisfies(own task) of the post-step state, episode_end = the queue
+ *     index the slot was on, end_pose = x | y << 8 | dir << 16 of the post-step state, and the
+ *     cursor moves on by craft_episode_begin's stride and wrap rule.
+ *       A next entry exists: the slot restarts exactly as under craft_step_stream (the entry's
+ *       scenario, pose and task, timer = max_timesteps, an empty inventory, nothing cleared; the
+ *       init pose and the spec craft_get_state reports become the entry's).  It is running:
+ *       episode_now is the new index, the obs row is features() of the new initial state, the
+ *       label the teacher's answer for it under the new task (-2 latches CRAFT_ETEACHER, because
+ *       the slot runs on).
+ *       None: the slot freezes as under craft_step_lang; the obs row and the label are those of
+ *       its final state, a -2 there does not latch, episode_now is -1.
+ *   not ended: done 0, success -1, episode_end and end_pose -1, episode_now the cursor.
+ * Statistics go to craft_stats as craft_step_lang counts them (stepped, ended, ended with success
+ * 1).  *any_live is set when some slot is not frozen after the tick, a restarted one included.
+ * CRAFT_EINVAL: step.flags != 0, use_alt without alt_actions, a misaligned obs, no
+ * craft_episode_begin since the queue was installed, or with label_out the BFS-queue limit
+ * (4*W*H > 1000) or a launch under stream capture while pool rows wait for their teacher-table
+ * entries (craft_sim_sync_table).  Always the one-tile kernel: craft_sim_tune_teach's lanes and
+ * table apply, craft_sim_tune's tile to the launch without a teacher.  craft_step*,
+ * craft_step_lang and craft_step_stream behave as before; the two stream ticks share one cursor
+ * per slot, so a handle may mix them. */
+typedef struct {
+  craft_lang_step_args_t step;   /* flags must be 0; label_out lives here */
+  int32_t* episode_end;          /* as craft_step_stream */
+  int32_t* end_pose;             /* pose of the final state: AFTER the ending step */
+  int32_t* episode_now;
+} craft_lang_stream_step_args_t;
+int craft_step_lang_stream(craft_sim_t* sim, const craft_lang_stream_step_args_t* args, void* stream);
+
 /* n_ticks consecutive craft_step ticks (tick0, tick0+1, ...) in one launch, with
  * results identical to n_ticks craft_step calls: each workgroup keeps its envs
  * on chip between ticks, so the per-tick prologue overlaps other workgroups'

@@ -127,6 +127,15 @@ class craft_stream_step_args_t(ctypes.Structure):
     ]
 
 
+class craft_lang_stream_step_args_t(ctypes.Structure):
+    _fields_ = [
+        ("step", craft_lang_step_args_t),
+        ("episode_end", ctypes.c_void_p),
+        ("end_pose", ctypes.c_void_p),
+        ("episode_now", ctypes.c_void_p),
+    ]
+
+
 class craft_rollout_teach_args_t(ctypes.Structure):
     _fields_ = [
         ("actions", ctypes.c_void_p),
@@ -190,6 +199,7 @@ SIGNATURES = {
     "craft_episode_queue": (_i32, [_vp, _vp, _i64]),
     "craft_episode_begin": (_i32, [_vp, _i64, _i64, _u32, _vp, _vp]),
     "craft_step_stream": (_i32, [_vp, ctypes.POINTER(craft_stream_step_args_t), _vp]),
+    "craft_step_lang_stream": (_i32, [_vp, ctypes.POINTER(craft_lang_stream_step_args_t), _vp]),
     "craft_rollout": (_i32, [_vp, _vp, _u64, _i64, _i32, _u32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "craft_rollout_teach": (_i32, [_vp, ctypes.POINTER(craft_rollout_teach_args_t), _vp]),
     "craft_stats": (_i32, [_vp, _vp, _i32, _vp]),

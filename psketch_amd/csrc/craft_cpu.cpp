@@ -28,6 +28,7 @@
 #include <thread>
 #include <vector>
 
+#include "craft_checks_lang_stream.h"
 #include "craft_host.h"
 
 namespace {
@@ -1139,6 +1140,108 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* /
           if (err) latch(s, err, i);
         }
         x->label_out[i] = label;
+      }
+    }
+    tot.add(acc);
+  });
+  tot.commit(s, p.any_live);
+  return CRAFT_OK;
+}
+
+// The language trainers' tick on the queue, written out on its own as well: the step comes first,
+// the ending tick's too, success is read off what it left, and only then the slot moves on.
+int craft_step_lang_stream(craft_sim_t* s, const craft_lang_stream_step_args_t* x, void* /*stream*/) {
+  if (!s || !x) return CRAFT_EINVAL;
+  const craft_lang_step_args_t& p = x->step;
+  if (const int rc = craft_host::check_step_lang_stream(facts(s), x, s->last_error)) return rc;
+  const int64_t count = (int64_t)s->queue.size();
+  TickTotals tot;
+  parallel_for(s, s->n_envs, [&](int64_t lo, int64_t hi) {
+    TickAcc acc;
+    std::vector<uint8_t> g(CRAFT_MAX_CELLS), row(s->F);
+    for (int64_t i = lo; i < hi; ++i) {
+      Agent a = unpack_state(s->state[i]);
+      if (!slot_valid(s, a)) {                         // never initialised by reset / set_state
+        latch(s, CRAFT_EINVAL, i);
+        invalid_slot_outputs(s, i, p.transition_code, p.obs, p.label_out, row.data());
+        continue;
+      }
+      uint8_t* iv = s->inv.data() + 32 * i;
+      uint32_t* m = s->mask.data() + 8 * i;
+      env_grid(s, i, a.scen, g.data());
+      const bool done_before = a.frozen != 0;
+      bool stepped = false, asked = false, ends = false, restarted = false;
+      int action = -1, code = -1, sat = -1;
+      int32_t ended_index = -1, ended_pose = -1;
+      if (!done_before) {
+        asked = p.use_alt && p.use_alt[i];
+        if (asked) action = p.alt_actions[i];
+        else if (p.actions) action = p.actions[i];
+        else action = hashed_action(s, p.action_seed, i, p.tick);
+        if (action < 0 || action >= CRAFT_N_ACTIONS) {
+          latch(s, CRAFT_EBADACTION, i);               // the slot and its cursor stay as they are
+        } else {
+          const int ox = a.x, oy = a.y;
+          bool ic = false, mc = false;
+          transition(s, g.data(), iv, a, m, action, ic, mc, i);
+          code = transition_code(ox, oy, a, ic);
+          stepped = true;
+          a.timer -= 1;
+          ends = action == CRAFT_STOP || a.timer <= 0;
+        }
+      }
+      if (ends || done_before) sat = satisfies(s, g.data(), iv, a, a.task);   // of the post-step state
+      if (ends) {
+        const int64_t cur = s->cursor[(size_t)i];
+        ended_index = (int32_t)cur;
+        ended_pose = (int32_t)((uint32_t)a.x | ((uint32_t)a.y << 8) | ((uint32_t)a.dir << 16));
+        int64_t next = -1;
+        if (cur >= 0) {
+          if (s->q_wrap) next = (cur + s->q_stride % count) % count;
+          else if (s->q_stride < count - cur) next = cur + s->q_stride;
+        }
+        s->cursor[(size_t)i] = next;
+        if (next >= 0) {                               // what the step grabbed or cleared goes with the old episode
+          const craft_sim::QueueEntry& e = s->queue[(size_t)next];
+          a.scen = e.scen; a.task = e.task; a.x = e.x; a.y = e.y; a.dir = e.dir;
+          a.timer = s->cfg.max_timesteps;
+          s->init[i] = (uint32_t)e.x | ((uint32_t)e.y << 8) | ((uint32_t)e.dir << 16);
+          std::memset(iv, 0, 32);
+          std::memset(m, 0, 32);
+          std::memcpy(g.data(), s->pool.data() + (size_t)a.scen * s->C, s->C);
+          restarted = true;
+        } else {                                       // run out: frozen as craft_step_lang leaves it
+          a.frozen = 1;
+          if (a.timer < 0) a.timer = 0;
+        }
+      }
+      if (stepped) s->state[i] = pack_state(a);
+      const bool is_done = ends || done_before;
+      if (p.done) p.done[i] = is_done ? 1 : 0;
+      if (p.success) p.success[i] = (int8_t)sat;
+      if (p.action_record) p.action_record[i] = stepped ? action : -1;
+      if (p.ask_record) p.ask_record[i] = (int8_t)(stepped ? (asked ? 1 : 0) : -1);
+      if (p.transition_code) p.transition_code[i] = (int8_t)code;
+      if (x->episode_end) x->episode_end[i] = ended_index;
+      if (x->end_pose) x->end_pose[i] = ended_pose;
+      if (x->episode_now) x->episode_now[i] = a.frozen ? -1 : (int32_t)s->cursor[(size_t)i];
+      acc.steps += stepped;
+      acc.ended += ends;
+      acc.succ += ends && sat == 1;
+      acc.any_live = acc.any_live || !a.frozen;
+      if (p.obs) {
+        features(s, g.data(), iv, a, row.data());
+        put_obs(s->k.obs_fmt, p.obs, i, s->F, row.data());
+      }
+      if (p.label_out) {
+        int label = -1;                                // done before the tick
+        if (!done_before) {
+          int len = -1, err = 0;
+          label = teach(s, g.data(), iv, a, a.task, false, len, err);
+          // an env that ended and froze: the rollout layer's call; one that restarted runs on
+          if (err && (!ends || restarted)) latch(s, err, i);
+        }
+        p.label_out[i] = label;
       }
     }
     tot.add(acc);

@@ -32,7 +32,9 @@ constexpr int kInvStride = 36;     // LDS bytes per inventory row (9 dwords: ban
 
 // MODE_LANG: the language trainers' tick (craft_step_lang): step first, then the timer
 // MODE_STREAM: MODE_TICK whose auto-reset takes the slot's next episode-queue entry (craft_step_stream)
-enum Mode { MODE_TICK = 0, MODE_TRANSITION = 1, MODE_OBSERVE = 2, MODE_RESET = 3, MODE_LANG = 4, MODE_STREAM = 5 };
+// MODE_LANG_STREAM: MODE_LANG on the episode queue: the ending tick steps, then the slot restarts (craft_step_lang_stream)
+enum Mode { MODE_TICK = 0, MODE_TRANSITION = 1, MODE_OBSERVE = 2, MODE_RESET = 3, MODE_LANG = 4, MODE_STREAM = 5,
+            MODE_LANG_STREAM = 6 };
 
 struct SimView {
   const uint8_t* pool;
@@ -221,7 +223,7 @@ struct TileArgs {
   int8_t* code;            // transition codes (craft_step_ex, craft_transition)
   int32_t* label;          // craft_step_teach: teacher label of every env's new state
   int8_t* ask;             // MODE_LANG: the use_alt bit of a slot that stepped, else -1
-  // MODE_STREAM (craft_step_stream), appended so that the other modes' argument words stay put:
+  // MODE_STREAM and MODE_LANG_STREAM (craft_step_stream, craft_step_lang_stream), appended so that the other modes' argument words stay put:
   // the packed queue (.x = scenario | task << 24, .y = x | y << 8 | dir << 16), each slot's
   // cursor (the queue index of its current episode, -1 once it has run out), the entries and
   // the index step to a slot's next episode (both < 2^31; craft_episode_begin reduces them),

@@ -1,6 +1,7 @@
 // craft_episode.h — the one definition of what every tick kernel must agree on: the per-env
 // body of ImitationTrainer.do_rollout (trainers/imitation.py:59-73) in pieces, the language
-// trainers' variant of it (tile_kernel's MODE_LANG), the episode queue's restart (MODE_STREAM),
+// trainers' variant of it (tile_kernel's MODE_LANG), the episode queue's restart (MODE_STREAM,
+// MODE_LANG_STREAM),
 // and the K-tick kernels' cleared-cell bookkeeping.
 //
 // Everything here is __device__ __forceinline__, works on state passed by reference, touches
@@ -96,6 +97,13 @@ __device__ __forceinline__ int32_t queue_next(int32_t cur, const uint32_t& count
 // action alone, so the next queue entry can be fetched beside the scenario row.
 __device__ __forceinline__ bool episode_ends(const Agent& s, int act) {
   return !s.frozen && (act == CRAFT_STOP || s.timer <= 1);
+}
+
+// The same for the language tick (craft_step_lang_stream): language_step_begin and
+// language_step_end will step and end the episode, so an action that is none of the six ends
+// nothing.
+__device__ __forceinline__ bool language_episode_ends(const Agent& s, int act) {
+  return !s.frozen && act >= 0 && act < CRAFT_N_ACTIONS && (act == CRAFT_STOP || s.timer <= 1);
 }
 
 // A packed queue entry (.x = scenario | task << 24, .y = the init word) as the agent's new

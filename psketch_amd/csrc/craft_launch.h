@@ -18,6 +18,9 @@ hipError_t launch_tick_lang(int tl, int nw, int win, int tile, const SimView& v,
                             hipStream_t st);
 hipError_t launch_tick_stream(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
                               hipStream_t st);
+// craft_tick_lang_stream.hip
+hipError_t launch_tick_lang_stream(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
+                                   hipStream_t st);
 hipError_t launch_queue_pack(const SimView& v, const int32_t* specs, int64_t count, uint2* out,
                              unsigned long long* first_bad, hipStream_t st);
 hipError_t launch_queue_begin(const uint2* entries, int64_t count, int64_t first_gid, int wrap, int64_t n,

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "craft_device.h"
+#include "craft_checks_lang_stream.h"
 #include "craft_host.h"
 #include "craft_launch.h"
 
@@ -1019,6 +1020,43 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* s
   const hipError_t e = craft::launch_tick_stream(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
                                                  reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(s, e, "craft_step_stream launch");
+  return CRAFT_OK;
+}
+
+int craft_step_lang_stream(craft_sim_t* s, const craft_lang_stream_step_args_t* x, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  int rc = craft_host::check_step_lang_stream(facts(s), x, s->last_error);
+  if (rc != CRAFT_OK) return rc;
+  const craft_lang_step_args_t& l = x->step;
+  TileArgs a{};
+  a.actions = l.actions;
+  a.ref = l.alt_actions;
+  a.bc = l.use_alt;
+  a.seed = l.action_seed;
+  a.tick = l.tick;
+  a.n = s->n_envs;
+  a.obs = l.obs;
+  a.done = l.done;
+  a.sat = l.success;
+  a.rec = l.action_record;
+  a.ask = l.ask_record;
+  a.code = l.transition_code;
+  a.any_live = l.any_live;
+  a.label = l.label_out;
+  a.q_entries = s->d_queue;
+  a.q_cursor = s->d_cursor;
+  a.q_count = (uint32_t)s->q_count;
+  a.q_step = s->q_step;
+  a.q_wrap = s->q_wrap;
+  a.ep_end = x->episode_end;
+  a.end_pose = x->end_pose;
+  a.ep_now = x->episode_now;
+  TickPlan p;
+  rc = tick_plan(s, l.label_out != nullptr, stream, "craft_step_lang_stream", p);
+  if (rc != CRAFT_OK) return rc;
+  const hipError_t e = craft::launch_tick_lang_stream(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
+                                                      reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(s, e, "craft_step_lang_stream launch");
   return CRAFT_OK;
 }
 

@@ -28,8 +28,11 @@ namespace craft {
 // MODE_STREAM (craft_step_stream) is MODE_TICK under auto-reset whose restart takes the slot's next
 // episode-queue entry: the lanes that restart (and only they) fetch the entry, reload their grid
 // row from the new scenario's pool row and, with a teacher, the scenario's teacher words.
+// MODE_LANG_STREAM (craft_step_lang_stream) is MODE_LANG on the queue: the ending tick steps like
+// any other, satisfies() reads the state that step left, and only then the slot restarts on its
+// next entry, so the step's inventory and mask writes and the restart meet in one lane.
 //
-// TL > 0 (MODE_TICK, MODE_LANG and MODE_STREAM only): TILE * TL more threads run the DemonstrationTeacher
+// TL > 0 (the four tick modes only): TILE * TL more threads run the DemonstrationTeacher
 // on every env's new state (craft_step_teach), TL lanes per env, while the first
 // tick threads stream the observations: the BFS reads the grid rows the tick left in
 // LDS.  NW = 32-bit words per cell set (teach_env).
@@ -85,7 +88,10 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
   // trip; beside teacher waves 10 (a 12x12 row's 9 chunks still at once): 16 took the 3x3 default
   // shape from 76 to 89 VGPRs, five waves per SIMD where the tick has six
   constexpr int kReloadBatch = TL > 0 ? 10 : 16;
-  constexpr bool kTick = kEp || MODE == MODE_LANG;                 // a rollout tick of either protocol
+  constexpr bool kLangQ = MODE == MODE_LANG_STREAM;                // the language tick on the episode queue
+  constexpr bool kLang = MODE == MODE_LANG || kLangQ;              // the language trainers' protocol
+  constexpr bool kQueue = MODE == MODE_STREAM || kLangQ;           // a tick that restarts slots from the queue
+  constexpr bool kTick = kEp || kLang;                             // a rollout tick of either protocol
 
   STAMP(0);
   // ---- A + C: wave 0, one lane per env ------------------------------------------------------
@@ -102,7 +108,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
     Agent s{};
     if (live) {
       const int64_t i = env0 + tid;
-      slot = (kEp || MODE == MODE_RESET || !a.src) ? i : (int64_t)a.src[i];
+      slot = (kEp || kLangQ || MODE == MODE_RESET || !a.src) ? i : (int64_t)a.src[i];
       dslot = (MODE == MODE_TRANSITION && a.dst) ? (int64_t)a.dst[i] : slot;
       if (slot < 0 || slot >= v.n_envs || dslot < 0 || dslot >= v.n_envs) {
         latch_error(v.err, CRAFT_ERANGE, i);
@@ -115,7 +121,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
     // (MODE_STREAM: the cursor and the action first.  With the state word they say whether the
     // episode ends, and the fetch of the next queue entry and the row loads behind it then wait
     // for these and the state, not for the inventory and the mask queued after them)
-    if (MODE == MODE_STREAM && live) {
+    if (kQueue && live) {
       cur = a.q_cursor[slot];
       if (a.actions) act = a.actions[slot];
       if (a.bc) {
@@ -198,6 +204,10 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       nxt = queue_next(cur, a.q_count, a.q_step, a.q_wrap);
       if (nxt >= 0) qe = a.q_entries[nxt];
     }
+    if (kLangQ && live && language_episode_ends(s, act)) {
+      nxt = queue_next(cur, a.q_count, a.q_step, a.q_wrap);
+      if (nxt >= 0) qe = a.q_entries[nxt];
+    }
     uint8_t* g = s_grid + tid * v.GS;
     uint32_t conn = 0, tcw0 = ~0u, tcw1 = ~0u;           // TL > 0: the scenario's free cells connected,
     if (TL > 0 && live) {                                  // its clearable cells the teacher table lists
@@ -247,6 +257,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
     int d = 0, succ = -1, counted = 0;
     int code = -1;                                         // transition code (craft.h)
     int was_frozen = 0;                                    // MODE_LANG: frozen before the tick
+    bool ended_here = false;                               // MODE_LANG_STREAM: ended this tick and froze (no next entry)
     if (live) {
       // The LDS row holds pool[scenario]; cells cleared this episode are applied
       // lazily, so an auto-reset (which restores exactly that row) needs no reload.
@@ -322,6 +333,53 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
         }
         // satisfies() of the state the step left (a slot frozen before: its final state)
         if (d) succ = satisfies(v, g, iv, s, s_task[s.task]);
+      } else if (kLangQ) {
+        // MODE_LANG's body, then the queue: the row already has the mask applied (restart is
+        // false above), so the ending step moves, grabs or crafts on the true grid
+        bool bad = false;
+        was_frozen = s.frozen;
+        language_step_begin(s, act, d, counted, bad);
+        if (bad) latch_error(v.err, CRAFT_EBADACTION, slot);
+        if (counted) {
+          const int ox = s.x, oy = s.y;
+          transition<TILE == 64>(v, s_rc, g, iv, s, m, act, inv_changed, mask_changed, rw[0], slot);
+          code = transition_code(ox, oy, s, inv_changed);
+          language_step_end(s, act, d);
+        }
+        // satisfies() of the state the step left, off the LDS row and inventory it just wrote
+        if (d) succ = satisfies(v, g, iv, s, s_task[s.task]);
+        const int64_t i = env0 + tid;
+        const bool ended = counted && d;
+        if (ended) {
+          if (a.ep_end) a.ep_end[i] = cur;
+          if (a.end_pose) a.end_pose[i] = (int32_t)pose_word(s);
+          a.q_cursor[slot] = nxt;
+          cur = nxt;
+        } else {
+          if (a.ep_end) a.ep_end[i] = -1;
+          if (a.end_pose) a.end_pose[i] = -1;
+        }
+        if (ended && nxt >= 0) {
+          // only now the next episode, as MODE_STREAM's restart; whatever the step wrote to the
+          // inventory and the mask goes with the old episode
+          restart_from_entry(s, qe, v.maxT);
+          s.frozen = 0;                                    // (language_step_end froze the slot)
+          if (TL > 0) {
+            conn = v.pool_conn[s.scen];
+            if (v.ttab) {
+              tcw0 = v.tt_cells[2 * (size_t)s.scen];
+              tcw1 = v.tt_cells[2 * (size_t)s.scen + 1];
+            }
+          }
+          reload_grid_row<kReloadBatch>(reinterpret_cast<const uint4*>(v.pool + (size_t)s.scen * v.CS),
+                                        reinterpret_cast<uint32_t*>(g), v.CS);
+          v.init[slot] = qe.y;
+#pragma unroll
+          for (int w = 0; w < 8; ++w) { ivw[w] = 0u; m[w] = 0u; }
+          inv_changed = mask_changed = true;
+        } else {
+          ended_here = ended;
+        }
       } else if (MODE == MODE_TRANSITION) {
         if (act >= CRAFT_N_ACTIONS) {
           latch_error(v.err, CRAFT_EBADACTION, slot);
@@ -358,14 +416,16 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
         const int64_t i = env0 + tid;
         store_outputs(a, i, d, succ, counted);
         if (a.rec) a.rec[i] = counted ? act : -1;        // action_seqs, imitation.py:59-61
-        if (MODE == MODE_STREAM && a.ep_now) a.ep_now[i] = s.frozen ? -1 : cur;
-        if (MODE == MODE_LANG && a.ask) a.ask[i] = (int8_t)(counted ? (a.bc && (bc & 0xffu)) : -1);
+        if (kQueue && a.ep_now) a.ep_now[i] = s.frozen ? -1 : cur;
+        if (kLang && a.ask) a.ask[i] = (int8_t)(counted ? (a.bc && (bc & 0xffu)) : -1);
       }
     }
     if ((kTick || MODE == MODE_TRANSITION) && a.code && tid < nE) a.code[env0 + tid] = (int8_t)code;
     // (MODE_LANG, bit 25: the episode ended this tick; the teacher still labels the slot, but what
     // the reference's teacher would raise there is the rollout layer's to report)
     s_agent[tid] = agent_word(s, live) | ((MODE == MODE_LANG && live && counted && d) ? (1u << 25) : 0u);
+    // (MODE_LANG_STREAM: only a slot that ended and did not restart; one that restarted runs on)
+    if (kLangQ && ended_here) s_agent[tid] |= 1u << 25;
     // the teacher's inputs: task | frozen << 8 (MODE_LANG: frozen before the tick, so a slot that
     // just ended is still labelled) | scenario connected << 9 | the teacher table has
     // this grid (craft_teach.h) << 10 | its table row << 11 (< 2^21 when the table is on)
@@ -374,7 +434,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
 #pragma unroll
       for (int w = 0; w < 8; ++w) ncl += __popc(m[w]);
       const int trow = live ? tt_index(v, s.scen, tcw0, tcw1, ncl, [&](int c) { return g[c] == 0; }) : -1;
-      s_tinfo[tid * tis] = (uint32_t)s.task | ((uint32_t)(MODE == MODE_LANG ? was_frozen : s.frozen) << 8) | (conn << 9) |
+      s_tinfo[tid * tis] = (uint32_t)s.task | ((uint32_t)(kLang ? was_frozen : s.frozen) << 8) | (conn << 9) |
                      (trow >= 0 ? (1u << 10) | ((uint32_t)trow << 11) : 0u);
     }
     if (kTick) {
@@ -382,7 +442,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       uint32_t n_succ = 0, n_end = 0, n_step = 0;
       tally_stats(live, counted, d, succ, n_succ, n_end, n_step);
       // (MODE_STREAM: a slot that restarted runs on, so the flag asks for slots not frozen)
-      const uint64_t bl = __ballot(MODE == MODE_STREAM ? (live && !s.frozen) : (live && counted && !d));
+      const uint64_t bl = __ballot(kQueue ? (live && !s.frozen) : (live && counted && !d));
       if (tid == 0) {
         add_stats(v, (int64_t)blockIdx.x, n_succ, n_end, n_step);
         if (a.any_live && bl) *a.any_live = 1;          // idempotent plain store
@@ -440,7 +500,7 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
                                    m0, s_inv + e * kInvStride, s, s.task, ql, false, len, err,
                                    ((ti >> 9) & 1u) != 0, (v.tt_fused && ((ti >> 10) & 1u)) ? tt_row(v, (int)(ti >> 11)) : nullptr,
                                    &defer, (v.tt_fused && ((ti >> 10) & 1u)) ? tt_row4(v, (int)(ti >> 11)) : nullptr);
-        if (err && ql == 0 && !(MODE == MODE_LANG && ((ag >> 25) & 1u))) latch_error(v.err, err, i);
+        if (err && ql == 0 && !(kLang && ((ag >> 25) & 1u))) latch_error(v.err, err, i);
         if (action == kTeachDeferred && ql == 0)
           s_work[kWs * __hip_atomic_fetch_add(&s_wctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)] =
               (uint32_t)e | ((uint32_t)defer << 8);
@@ -458,8 +518,8 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
 #ifdef CRAFT_STAMPS_TT      // diagnostic: 1 the teacher's walks done, 2 its dense pass done, 4 E done
     if (tid == NT && v.stamps) v.stamps[8 * (int64_t)blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
 #endif
-    teach_deferred_dense<NW, TL, MODE == MODE_LANG>(v, s_work, (int)nw, u, TILE * TL, s_grid, v.GS, s_agent, s_tinfo,
-                                                    a.label + env0, env0, kWs, tis);
+    teach_deferred_dense<NW, TL, kLang>(v, s_work, (int)nw, u, TILE * TL, s_grid, v.GS, s_agent, s_tinfo,
+                                        a.label + env0, env0, kWs, tis);
 #ifdef CRAFT_STAMPS_TT
     STAMP_MAX(2);
 #endif

@@ -22,7 +22,7 @@ import torch
 
 from . import _native as N
 from .language import WORDS
-from .rollout import RolloutError, _live_flags
+from .rollout import EvalContext, EvalInfo, RolloutError, _live_flags, _queue_pass  # noqa: F401
 
 MODES = ("primitive", "interactive", "active")
 PAD = "<PAD>"
@@ -195,6 +195,48 @@ def do_language_rollout(sim, spec, student, teacher, is_eval, mode, ref_actions=
         student.imitate_instructed()
     num_steps = int((p.seqs[:t] >= 0).sum()) if train else 0
     return _summary(sim, task, p, num_interactions, num_steps, raised)
+
+
+def evaluate(sim, specs, act, ids=None, max_ticks=None):
+    """The reference's evaluate of its three language trainers, one pass over `specs`.  They
+    inherit ImitationTrainer.evaluate (trainers/primitive_language.py:14, imitation.py:183-226),
+    which loops over THEIR do_rollout(..., is_eval=True); in eval mode the three run the same env
+    loop (student.act, step, then the timer), so this one function serves them.  It is
+    rollout.evaluate on craft_step_lang_stream: the same arguments, the same EvalContext for
+    `act` (episode, tick, restarted), the same static slot assignment (slot i runs rows i,
+    i + n, ...), the same padding of a split shorter than n_envs, and it returns an EvalInfo.
+    What differs is the protocol: an episode that times out takes max_timesteps steps, the
+    ending tick steps like any other, success is satisfies() of the state that step left, and a
+    failed get episode's distance is measured from the pose after it (end_pose), on the
+    initial grid (primitive_language.py:121-133).  Per instance the results equal
+    do_language_rollout(is_eval=True) on any batching; no slot idles until the slowest env of
+    its batch is done.
+
+    A training loop that feeds a student an endless stream of fresh episodes drives the same
+    tick itself, with wrap=True, and reads what do_language_rollout reads per tick:
+
+        sim.set_episode_queue(specs)
+        obs = sim.empty_obs()
+        sim.begin_episodes(wrap=True, obs=obs)
+        labels, _ = sim.teacher()                      # the instruction for every initial state
+        new = torch.empty_like(labels)
+        rec = torch.empty(n, dtype=torch.int32, device=dev)
+        codes = torch.empty(n, dtype=torch.int8, device=dev)
+        ended = torch.empty(n, dtype=torch.int32, device=dev)
+        for t in range(steps):
+            actions, ask = student.act(obs, t)         # the active student's own action and ASK bit
+            student.set_instructions(labels)           # (a -2 label: the reference's teacher raised)
+            follow = student.instructed_act(obs, t, ask)
+            sim.step_lang_stream(actions, tick=t, alt_actions=follow, use_alt=ask, obs=obs,
+                                 labels=new, action_record=rec, transition_code=codes,
+                                 episode_end=ended)
+            # rec / codes -> PrimitiveLanguageTeacher.describe_batch, as in do_language_rollout;
+            # ended >= 0: the slot began a new episode, `obs` and `new` are its initial state's
+            labels = new.clone()                       # every slot runs on: no -1 under wrap
+
+    Under wrap no slot freezes, so every label is the teacher's answer for the state the student
+    sees next, a restarted slot's for its new task."""
+    return _queue_pass(sim, specs, act, ids, max_ticks, lang=True)
 
 
 def _primitive(sim, spec, task, student, teacher, is_eval, ref_actions):

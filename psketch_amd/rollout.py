@@ -493,6 +493,13 @@ def evaluate(sim, specs, act, ids=None, max_ticks=None):
     initial grid at the final pose) are computed after the pass, n_envs at a time, with
     set_state + teacher(path_len_out=): the simulator's slots are overwritten.
     Raises RolloutError where the reference raises (success None; no reachable target)."""
+    return _queue_pass(sim, specs, act, ids, max_ticks, lang=False)
+
+
+def _queue_pass(sim, specs, act, ids, max_ticks, lang):
+    """evaluate()'s pass over the queue under either protocol: craft_step_stream (the imitation
+    trainer's), or with `lang` craft_step_lang_stream (the language trainers':
+    language_rollout.evaluate).  The two argument structs name their shared fields alike."""
     n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
     if isinstance(specs, (tuple, list)) and len(specs) == 5 and np.ndim(specs[0]) == 1:
         specs = np.stack([np.asarray(torch.as_tensor(a).cpu()) for a in specs], 1)
@@ -521,11 +528,12 @@ def evaluate(sim, specs, act, ids=None, max_ticks=None):
     ctx = EvalContext(torch.arange(n, **i32), torch.zeros(n, **i32), torch.ones(n, **i32))
     flags, flag_dev, events = _live_flags(sim, max_ticks)
     live = None if flag_dev else torch.zeros(max_ticks + 1, **i32)
-    args = N.craft_stream_step_args_t()
-    args.step.flags = N.STEP_AUTORESET
+    what = "craft_step_lang_stream" if lang else "craft_step_stream"
+    args = N.craft_lang_stream_step_args_t() if lang else N.craft_stream_step_args_t()
+    args.step.flags = 0 if lang else N.STEP_AUTORESET
     args.step.obs = obs.data_ptr()
     args.episode_now = now.data_ptr()
-    fn, h, pargs = sim._L.craft_step_stream, sim._h, ctypes.byref(args)
+    fn, h, pargs = getattr(sim._L, what), sim._h, ctypes.byref(args)
     t = 0
     running = True
     while running and t < max_ticks:
@@ -542,7 +550,7 @@ def evaluate(sim, specs, act, ids=None, max_ticks=None):
         args.end_pose = pose[t].data_ptr()
         st = fn(h, pargs, sim._stream())
         if st:
-            N.check(st, h, "craft_step_stream", L=sim._L)
+            N.check(st, h, what, L=sim._L)
         # the next call's context, on the device
         began = ended[t] >= 0
         ctx = EvalContext(now.clone(), torch.where(began, 0, ctx.tick + 1).to(torch.int32),
@@ -557,12 +565,17 @@ def evaluate(sim, specs, act, ids=None, max_ticks=None):
         raise RuntimeError(f"evaluate: slots still running after {t} ticks")
     sim.check()                                  # an error latched during the pass
     return _eval_summary(sim, specs, ids, rec[:t].cpu().numpy(), ended[:t].cpu().numpy(),
-                         pose[:t].cpu().numpy(), succ[:t].cpu().numpy(), t)
+                         pose[:t].cpu().numpy(), succ[:t].cpu().numpy(), t,
+                         ("primitive_language.py:124", "primitive_language.py:129-131") if lang
+                         else ("imitation.py:68", "imitation.py:88-89"))
 
 
-def _eval_summary(sim, specs, ids, rec, ended, pose, succ, ticks):
+def _eval_summary(sim, specs, ids, rec, ended, pose, succ, ticks, lines):
     """evaluate()'s per-instance results from the pass's per-tick records ([ticks, n] each: the
-    action taken, the queue index of an episode that ended, its final pose and success)."""
+    action taken, the queue index of an episode that ended, its final pose and success).  The
+    same under both protocols: the ending tick's record is the episode's last action, and the
+    pose is the final state's (the language protocol's: after the ending step).  lines: where
+    the reference raises, for the two messages."""
     n, T, count = sim.n_envs, sim.config.max_timesteps, len(specs)
     seqs = np.full((count, T), -1, dtype=np.int32)
     n_actions = np.zeros(count, dtype=np.int32)
@@ -584,7 +597,7 @@ def _eval_summary(sim, specs, ids, rec, ended, pose, succ, ticks):
     if (success == -2).any():
         raise RuntimeError(f"evaluate: instance {int(np.argmax(success == -2))} was never finished")
     if (success < 0).any():
-        raise RolloutError("satisfies() returned None for a finished episode (imitation.py:68)")
+        raise RolloutError(f"satisfies() returned None for a finished episode ({lines[0]})")
     goals = np.asarray([t.goal_name == "get" for t in sim.task_manager.tasks])
     is_get = goals[specs[:, 4]]
     distances = np.where(is_get, 0, -1).astype(np.int32)
@@ -607,7 +620,7 @@ def _eval_summary(sim, specs, ids, rec, ended, pose, succ, ticks):
             if e.status != N.ETEACHER:
                 raise
     if (distances[failed] < 0).any():
-        raise RolloutError("find_closest_resources found no target: len(None) (imitation.py:88-89)")
+        raise RolloutError(f"find_closest_resources found no target: len(None) ({lines[1]})")
     eval_info = {ids[e]: {"actions": [int(a) for a in seqs[e, :n_actions[e]]], "success": int(success[e])}
                  for e in range(count)}
     if len(eval_info) != count:

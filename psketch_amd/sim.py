@@ -450,6 +450,41 @@ class CraftSim:
                     "craft_step_stream")
         return obs
 
+    def step_lang_stream(self, actions=None, seed=0, tick=0, alt_actions=None, use_alt=None, obs=None,
+                         done=None, success=None, action_record=None, ask_record=None,
+                         transition_code=None, any_live=None, labels=None, episode_end=None,
+                         end_pose=None, episode_now=None, flags=0):
+        """step_lang on the episode queue (craft_step_lang_stream): every running slot steps
+        first, the ending tick included, success is satisfies() of the state that step left, and
+        a slot whose episode ended then restarts on its next queue entry.  step_lang's arguments
+        plus step_stream's three int32 [N] outputs: episode_end, end_pose (the pose AFTER the
+        ending step) and episode_now.  labels: -1 for a slot frozen before the tick; a slot that
+        restarted gets the teacher's answer for its new initial state and task."""
+        n = self.n_envs
+        args = N.craft_lang_stream_step_args_t()
+        keep = []
+        st = args.step
+        _put(st, keep, "actions", self._i32(actions, n) if actions is not None else None)
+        _put(st, keep, "alt_actions", self._i32(alt_actions, n) if alt_actions is not None else None)
+        if use_alt is not None:
+            _put(st, keep, "use_alt", self._flag_mask("use_alt", use_alt, n))
+        self._put_bufs(st, keep, (("done", done, torch.uint8, (n,)),
+                                  ("success", success, torch.int8, (n,)),
+                                  ("action_record", action_record, torch.int32, (n,)),
+                                  ("ask_record", ask_record, torch.int8, (n,)),
+                                  ("transition_code", transition_code, torch.int8, (n,)),
+                                  ("any_live", any_live, torch.int32, (1,)),
+                                  ("label_out", labels, torch.int32, (n,)),
+                                  ("obs", obs, self.obs_dtype, (n, self.n_features))))
+        st.action_seed = seed & (2**64 - 1)
+        st.tick = int(tick)
+        st.flags = int(flags)
+        self._put_bufs(args, keep, [(name, t, torch.int32, (n,)) for name, t in (
+            ("episode_end", episode_end), ("end_pose", end_pose), ("episode_now", episode_now))])
+        self._check(self._L.craft_step_lang_stream(self._h, ctypes.byref(args), self._stream()),
+                    "craft_step_lang_stream")
+        return obs
+
     def rollout(self, n_ticks, seed=0, tick0=0, actions=None, autoreset=True, obs=None,
                 reward=None, done=None, success=None):
         """n_ticks craft_step ticks in one launch (include/craft.h craft_rollout),
