@@ -357,7 +357,9 @@ static hipError_t launch_rollout_one(const SimView& v, const RolloutArgs& a, siz
 }
 
 // The split-producer kernel (craft_rollout_split.h) for 16- and 32-env tiles: NT threads =
-// C wave + D wave + NT / 64 - 2 streaming waves, 5 waves per SIMD.
+// C wave + D wave + NT / 64 - 2 streaming waves (3x3 32-env tiles on 512 threads: two D waves and
+// five streaming waves); built for CRAFT_SPLIT_WPE = 4 waves per SIMD at 3x3 (128 VGPRs, two
+// 512-thread workgroups per CU), 2 at wider windows.
 template <int WIN, int TILE, int NT, int FMT, bool GIVEN>
 static hipError_t launch_rollout_split_one(const SimView& v, const RolloutArgs& a, hipStream_t st) {
   const int64_t tiles = (v.n_envs + TILE - 1) / TILE;

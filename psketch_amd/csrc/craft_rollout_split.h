@@ -4,9 +4,11 @@
 // Small tiles need their own transition latency chain each, so one wave doing
 // both the transition and the scatter cannot keep up.  Here:
 //   wave 0        C(j+1): the transitions (one lane per env);
-//   wave 1        D(j):   the observation scatter of the item before (64 / TILE
-//                         lanes per env) into LDS row buffer j & 1;
-//   waves 2..     E(j-1): stream the rows of the item before that to HBM and
+//   wave 1 (3x3 32-env tiles on 512 threads: waves 1 and 2)
+//                 D(j):   the observation scatter of the item before (64 / TILE
+//                         lanes per env; four on those two waves) into LDS row
+//                         buffer j & 1;
+//   the rest      E(j-1): stream the rows of the item before that to HBM and
 //                         clear them.
 // One workgroup barrier per interval.  An "item" is one tick of one tile.
 //
@@ -59,8 +61,12 @@ __host__ __device__ inline int split_lds_bytes(int tile, int GS, int F, int CS, 
 template <int WIN, int TILE, int NT, int FMT, int WPE, bool GIVEN, bool FLAT = false>
 __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  static_assert(NT >= 192 && TILE <= 64, "a producer, a scatter wave and at least one streaming wave");
-  constexpr int P = 64 / TILE;                            // scatter lanes per env
+  // scatter waves: two for 3x3 windows on 32-env tiles at 512 threads (four lanes per env, one of
+  // scatter_env_part's four units each), one everywhere else (two units per lane there)
+  constexpr int DW = (WIN == 3 && TILE == 32 && NT == 512) ? 2 : 1;
+  constexpr int E0 = 64 + 64 * DW;                        // the first streaming thread
+  static_assert(NT >= E0 + 64 && TILE <= 64, "a producer, the scatter waves and at least one streaming wave");
+  constexpr int P = 64 * DW / TILE;                       // scatter lanes per env
   auto up16 = [](int x) { return (x + 15) & ~15; };
   const int GS = v.GS, F = v.F;
   // the recipe words in a VGPR (lane w: word w), loaded while every lane is active, for the
@@ -269,19 +275,19 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
     const int64_t env0 = (int64_t)t * TILE;
     const int nE = (int)min((int64_t)TILE, n - env0);
     const int64_t r = (a.tick0 + k) % a.ring;
-    if (outs && tid - 128 < nE) {                       // the tick's done / success / reward (flat pipeline)
-      const uint32_t w = s_out[(p & 3) * TILE + tid - 128];
+    if (outs && tid - E0 < nE) {                        // the tick's done / success / reward (flat pipeline)
+      const uint32_t w = s_out[(p & 3) * TILE + tid - E0];
       // (pack_outputs' word taken apart in place, not through a helper: as one, the continuous
       // pipeline's instantiation took one more VGPR)
       if (w >> 24) {
-        const int64_t o = r * n + env0 + (tid - 128);
+        const int64_t o = r * n + env0 + (tid - E0);
         if (a.done) a.done[o] = (uint8_t)(w & 0xffu);
         if (a.sat) a.sat[o] = (int8_t)((w >> 8) & 0xffu);
         if (a.reward) a.reward[o] = ((w >> 16) & 1u) ? 1.0f : 0.0f;
       }
     }
     void* out = static_cast<uint8_t*>(a.obs) + r * n * (int64_t)F * esz;
-    stream_obs<FMT, NT - 128, true>(s_obs + (p & 1) * obs_buf, out, env0, F, nE, v.obs_policy, tid - 128);
+    stream_obs<FMT, NT - E0, true>(s_obs + (p & 1) * obs_buf, out, env0, F, nE, v.obs_policy, tid - E0);
   };
 
   // ---- once per workgroup: task table, cleared observation rows --------------------------------
@@ -456,7 +462,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
         produce(i + 1);
         if (interval_end(i, w0)) break;
       }
-    } else if (tid < 128) {
+    } else if (tid < E0) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
@@ -487,7 +493,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
         row[8] = acc_vm; row[9] = acc_pub; row[10] = acc_ld; row[11] = acc_dma;
       } else if (tid == 64) {
         row[3] = acc_work; row[4] = acc_wait;
-      } else if (tid == 128) {
+      } else if (tid == E0) {
         row[5] = acc_work;
       }
     }
@@ -593,7 +599,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
       } else {
         if (want_obs) {
           __syncthreads();                              // C(0) complete
-          if (tid < 128) {
+          if (tid < E0) {
 #pragma unroll 1
             for (int i = 0; i <= nq; ++i) {
               if (i < nq) scatter_d(i, nE);
@@ -603,7 +609,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
             for (int i = 0; i <= nq; ++i) {
               if (i >= 1) stream_e(i - 1, t, k0 + i - 1, false);
 #ifdef CRAFT_STAMPS
-              if (tid == 128 && srow_t && n_done == 0 && i == 1) srow_t[13] = __builtin_amdgcn_s_memrealtime();
+              if (tid == E0 && srow_t && n_done == 0 && i == 1) srow_t[13] = __builtin_amdgcn_s_memrealtime();
 #endif
               __syncthreads();
             }
