@@ -519,6 +519,43 @@ int craft_rollout(craft_sim_t* sim, const int32_t* actions, uint64_t action_seed
                   int32_t n_ticks, uint32_t flags, void* obs, int32_t ring, float* reward,
                   uint8_t* done, int8_t* success, void* stream);
 
+/* craft_rollout on the episode queue: n_ticks consecutive craft_step_stream ticks (tick0,
+ * tick0 + 1, ...; label_out NULL) in one launch, with results identical to those n_ticks calls
+ * with the same actions: every output row of every tick, each slot's state, inventory, cleared
+ * cells, init pose and spec as craft_get_state reports them, its queue cursor, the craft_stats
+ * counters and the latched error.  A slot whose episode ends restarts on its next queue entry in
+ * the middle of the launch, any number of times.  For rollouts over many scenarios whose actions
+ * do not depend on the observations: the hashed draw, or recorded action sequences replayed into
+ * observations (Python: rollout.replay).  `actions` is device int32[n_ticks][n_envs] or NULL for
+ * the hashed draw; tick t writes ring slot t % ring of every output (each may be NULL); n_ticks
+ * == 0 is a no-op.  The cursor is the one craft_step_stream and craft_step_lang_stream move, so a
+ * handle may mix the three between launches.
+ * CRAFT_EINVAL: flags != CRAFT_STEP_AUTORESET, no craft_episode_begin since the queue was
+ * installed, n_ticks < 0, ring < 1, tick0 < 0, or an obs ring slot that is not 16-byte aligned.
+ * Launch shape: always the split-producer kernel on 512 threads, one work unit per tile for the
+ * whole launch, on 32-env tiles; 16-env tiles where craft_sim_tune chose 16 or where two staged
+ * observation buffers of 32 envs do not fit a workgroup's LDS.  craft_sim_tune_rollout's chunk
+ * and threads knobs do not apply; craft_sim_tune's store policy does.  Ordering and graph capture
+ * as craft_rollout: the launches share its work-unit counter (one stream, or streams the caller
+ * orders), a captured launch uses the graph's own counter and the memset captured with it, and
+ * nothing is allocated on the step path. */
+typedef struct {
+  const int32_t* actions;   /* int32[n_ticks][n_envs], or NULL: the hashed draw */
+  uint64_t action_seed;
+  int64_t  tick0;
+  int32_t  n_ticks;
+  uint32_t flags;           /* must be CRAFT_STEP_AUTORESET */
+  int32_t  ring;            /* ring slots of every output (>= 1); tick t writes slot t % ring */
+  void*    obs;             /* [ring][n_envs][n_features], obs format, each slot 16-byte aligned */
+  float*   reward;          /* [ring][n_envs] */
+  uint8_t* done;
+  int8_t*  success;
+  int32_t* episode_end;     /* [ring][n_envs], as craft_step_stream's */
+  int32_t* end_pose;
+  int32_t* episode_now;
+} craft_rollout_stream_args_t;
+int craft_rollout_stream(craft_sim_t* sim, const craft_rollout_stream_args_t* args, void* stream);
+
 /* craft_rollout with the DemonstrationTeacher in the same launch: n_ticks ticks, and after each
  * one DemonstrationTeacher.__call__ (teachers/demonstration.py:9-30) of every slot's new state,
  * as n_ticks craft_step_teach calls would give, with each tick's action taken per slot from

@@ -136,6 +136,24 @@ class craft_lang_stream_step_args_t(ctypes.Structure):
     ]
 
 
+class craft_rollout_stream_args_t(ctypes.Structure):
+    _fields_ = [
+        ("actions", ctypes.c_void_p),
+        ("action_seed", ctypes.c_uint64),
+        ("tick0", ctypes.c_int64),
+        ("n_ticks", ctypes.c_int32),
+        ("flags", ctypes.c_uint32),
+        ("ring", ctypes.c_int32),
+        ("obs", ctypes.c_void_p),
+        ("reward", ctypes.c_void_p),
+        ("done", ctypes.c_void_p),
+        ("success", ctypes.c_void_p),
+        ("episode_end", ctypes.c_void_p),
+        ("end_pose", ctypes.c_void_p),
+        ("episode_now", ctypes.c_void_p),
+    ]
+
+
 class craft_rollout_teach_args_t(ctypes.Structure):
     _fields_ = [
         ("actions", ctypes.c_void_p),
@@ -201,6 +219,7 @@ SIGNATURES = {
     "craft_step_stream": (_i32, [_vp, ctypes.POINTER(craft_stream_step_args_t), _vp]),
     "craft_step_lang_stream": (_i32, [_vp, ctypes.POINTER(craft_lang_stream_step_args_t), _vp]),
     "craft_rollout": (_i32, [_vp, _vp, _u64, _i64, _i32, _u32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "craft_rollout_stream": (_i32, [_vp, ctypes.POINTER(craft_rollout_stream_args_t), _vp]),
     "craft_rollout_teach": (_i32, [_vp, ctypes.POINTER(craft_rollout_teach_args_t), _vp]),
     "craft_stats": (_i32, [_vp, _vp, _i32, _vp]),
     "craft_transition": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "craft_checks_lang_stream.h"
+#include "craft_checks_rollout_stream.h"
 #include "craft_host.h"
 
 namespace {
@@ -1269,6 +1270,32 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
     in.done = done ? done + r * n : nullptr;
     in.sat = success ? success + r * n : nullptr;
     run_ticks(s, in, nullptr);
+  }
+  return CRAFT_OK;
+}
+
+// craft_rollout_stream: tick by tick, each a craft_step_stream into its ring slot, the way
+// craft_rollout above is a loop of ticks
+int craft_rollout_stream(craft_sim_t* s, const craft_rollout_stream_args_t* x, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_rollout_stream(facts(s), x, s->last_error)) return rc;
+  const int esz = craft_host::obs_elem_size(s->k.obs_fmt);
+  const int64_t n = s->n_envs;
+  for (int32_t k = 0; k < x->n_ticks; ++k) {
+    const int64_t r = (x->tick0 + k) % x->ring;      // tick t writes ring slot t % ring
+    craft_stream_step_args_t t{};
+    t.step.actions = x->actions ? x->actions + (int64_t)k * n : nullptr;
+    t.step.action_seed = x->action_seed;
+    t.step.tick = x->tick0 + k;
+    t.step.flags = x->flags;
+    t.step.obs = x->obs ? static_cast<uint8_t*>(x->obs) + r * n * s->F * esz : nullptr;
+    t.step.reward = x->reward ? x->reward + r * n : nullptr;
+    t.step.done = x->done ? x->done + r * n : nullptr;
+    t.step.success = x->success ? x->success + r * n : nullptr;
+    t.episode_end = x->episode_end ? x->episode_end + r * n : nullptr;
+    t.end_pose = x->end_pose ? x->end_pose + r * n : nullptr;
+    t.episode_now = x->episode_now ? x->episode_now + r * n : nullptr;
+    if (const int rc = craft_step_stream(s, &t, stream)) return rc;
   }
   return CRAFT_OK;
 }

@@ -28,6 +28,9 @@ hipError_t launch_queue_begin(const uint2* entries, int64_t count, int64_t first
 // craft_rollout_w3.hip, craft_rollout_teach.hip
 hipError_t launch_rollout(int win, int tile, int threads, const SimView& v, const RolloutArgs& a, size_t lds,
                           hipStream_t st);
+// craft_rollout_stream.hip: 512 threads on rollout_stream_tile's 32- or 16-env tiles
+int rollout_stream_tile(int tile_knob, const SimView& v);
+hipError_t launch_rollout_stream(int win, int tile, const SimView& v, const RolloutArgs& a, hipStream_t st);
 hipError_t launch_rollout_teach(int win, int nw, const SimView& v, const RolloutArgs& a, hipStream_t st);
 // craft_teacher.hip
 hipError_t launch_teacher(int nw, int lanes, const SimView& v, const int32_t* slots, const int32_t* tasks,

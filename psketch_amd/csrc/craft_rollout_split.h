@@ -32,6 +32,17 @@
 // item copies the whole row across.  Everything else (outputs, statistics) is as
 // in craft_rollout.h, and the results are identical (the same tests run both
 // kernels).
+//
+// QUEUE (craft_rollout_stream).  The same per-unit pipeline on the episode queue: a slot whose
+// episode ends takes its next queue entry (craft_episode.h: queue_next, restart_from_entry) and
+// wave 0 reloads its pristine row and the item's grid row from pool[scenario] in the middle of
+// the unit, or freezes when the queue has none.  `chg` records the reload as a third kind of
+// change, and the next C on the other parity buffer copies the whole row across, as a freshly
+// loaded tile's second item does.  Only wave 0 reads the pristine rows, and the scatter wave
+// reads only the grid buffer of the item C has finished, so nothing else is double-buffered.
+// Every restart reloads the row, so no ClearList is kept.  The tick's episode_end / end_pose /
+// episode_now go out from wave 0 beside done / success / reward; the unit's end also publishes
+// the init word and the cursor.  One unit per tile for the whole launch, never FLAT.
 #pragma once
 #include <type_traits>
 
@@ -58,9 +69,10 @@ __host__ __device__ inline int split_lds_bytes(int tile, int GS, int F, int CS, 
 // FLAT: the continuous pipeline (one unit per tile, observations on: RolloutArgs.flat);
 // otherwise work units from the queue.  Separate instantiations, so that neither path's
 // registers count against the other.
-template <int WIN, int TILE, int NT, int FMT, int WPE, bool GIVEN, bool FLAT = false>
+template <int WIN, int TILE, int NT, int FMT, int WPE, bool GIVEN, bool FLAT = false, bool QUEUE = false>
 __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  static_assert(!(QUEUE && FLAT), "the queue variant runs work units, one per tile");
   // scatter waves: two for 3x3 windows on 32-env tiles at 512 threads (four lanes per env, one of
   // scatter_env_part's four units each), one everywhere else (two units per lane there)
   constexpr int DW = (WIN == 3 && TILE == 32 && NT == 512) ? 2 : 1;
@@ -104,6 +116,10 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
   ClearList clr_prev;        // the episode's clears before a restart (for the other buffer)
   uint32_t chg = 0;          // what the last C did to its buffer: 0 nothing, 1 + cell cleared, kRestart
   constexpr uint32_t kRestart = 0x80000000u;
+  constexpr uint32_t kReload = 0x40000000u;   // QUEUE: the row was reloaded from another pool row
+  int32_t cur = -1;          // QUEUE: the slot's queue cursor (craft_episode.h)
+  uint2 qe = make_uint2(0u, 0u);   // and the entry after it, fetched an episode ahead: a restart then
+                                   // waits for one L2 round trip (the pool row), not for two in a row
   int sync = 0;              // how C brings its buffer up to date: 0 loaded, 1 whole copy, 2 from chg
   bool live = false;
   int64_t slot = 0;
@@ -122,7 +138,12 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
     s = unpack_state(st);
     if (live) {
       // bring this buffer up to the other buffer's state: whole row after a load, else its last change
-      if (sync == 1) {
+      if constexpr (QUEUE) {
+        // (a restart is always a reload here: the other buffer's row as a whole, as after a load)
+        if (sync == 1 || chg == kReload)
+          copy_row_words(reinterpret_cast<uint32_t*>(g), reinterpret_cast<const uint32_t*>(grid_of(p ^ 1)), v.CS);
+        else if (chg) g[chg - 1] = 0;
+      } else if (sync == 1) {
         copy_row_words(reinterpret_cast<uint32_t*>(g), reinterpret_cast<const uint32_t*>(grid_of(p ^ 1)), v.CS);
       } else if (sync == 2) {
         if (chg == kRestart) clr_prev.restore(g, pw, v.CS);
@@ -142,7 +163,31 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
       bool restart = false;
       protocol_step(s, act, a.flags, d, counted, restart);
       if (d) succ = satisfies(v, g, iv, s, task_word);  // of the pre-step state
-      if (restart) {
+      int32_t ended = -1, epose = -1;                   // QUEUE: the tick's episode_end and end_pose
+      if constexpr (QUEUE) {
+        if (restart) {
+          // the slot's next episode, as tile_kernel's MODE_STREAM takes it: the entry's scenario,
+          // pose and task, an empty inventory, pool[scenario] as the pristine row and this item's
+          // grid row; without a next entry the slot freezes and its cursor becomes -1
+          ended = cur;
+          epose = (int32_t)pose_word(s);
+          cur = queue_next(cur, a.q_count, a.q_step, a.q_wrap);
+          if (cur >= 0) {
+            restart_from_entry(s, qe, v.maxT);
+            task_word = s_task[s.task];
+            init_word = qe.y;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) reinterpret_cast<uint32_t*>(iv)[w] = 0u;
+            load_pool_row(reinterpret_cast<const uint4*>(v.pool + (size_t)s.scen * v.CS),
+                          reinterpret_cast<uint32_t*>(s_pristine + tid * GS), reinterpret_cast<uint32_t*>(g), v.CS);
+            chg = kReload;
+            const int32_t nxt = queue_next(cur, a.q_count, a.q_step, a.q_wrap);
+            if (nxt >= 0) qe = a.q_entries[nxt];        // (behind the row's loads: nothing waits for it here)
+          } else {
+            freeze_agent(s);
+          }
+        }
+      } else if (restart) {
         restart_agent(s, init_word, v.maxT);
 #pragma unroll
         for (int w = 0; w < 8; ++w) reinterpret_cast<uint32_t*>(iv)[w] = 0u;
@@ -161,12 +206,17 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
         else transition<true>(v, s_rc, g, iv, s, m_unused, act, inv_changed, mask_changed, rcv, slot);
         if (mask_changed) {
           chg = 1u + (uint32_t)fc;
-          clr.push(fc);
+          if constexpr (!QUEUE) clr.push(fc);
         }
       }
       st = pack_state(s);
       if (lds_out) s_out[(p & 3) * TILE + tid] = pack_outputs(d, succ, counted);   // stored by the streaming waves with E
       else store_outputs(a, r * n + slot, d, succ, counted);
+      if constexpr (QUEUE) {
+        if (a.ep_end) a.ep_end[r * n + slot] = ended;
+        if (a.end_pose) a.end_pose[r * n + slot] = epose;
+        if (a.ep_now) a.ep_now[r * n + slot] = s.frozen ? -1 : cur;
+      }
     } else if (lds_out && tid < TILE) {
       s_out[(p & 3) * TILE + tid] = 0u;
     }
@@ -205,8 +255,13 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
       } else {
         st = v.state[slot];
         init_word = v.init[slot];
+        if constexpr (QUEUE) cur = a.q_cursor[slot];
         i0 = v.inv[2 * slot]; i1 = v.inv[2 * slot + 1];
         m0 = v.mask[2 * slot]; m1 = v.mask[2 * slot + 1];
+        if constexpr (QUEUE) {                          // (last: it waits for the cursor)
+          const int32_t nxt = queue_next(cur, a.q_count, a.q_step, a.q_wrap);
+          if (nxt >= 0) qe = a.q_entries[nxt];
+        }
       }
       ivr[0] = i0.x; ivr[1] = i0.y; ivr[2] = i0.z; ivr[3] = i0.w;
       ivr[4] = i1.x; ivr[5] = i1.y; ivr[6] = i1.z; ivr[7] = i1.w;
@@ -258,6 +313,10 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
     uint32_t m[8];
     cleared_mask(pw, reinterpret_cast<const uint32_t*>(grid_of(p)), v.C, m);
     publish_state(v, slot, st, reinterpret_cast<const uint32_t*>(inv_of(p)), m, sc1);
+    if constexpr (QUEUE) {                              // the spec the slot ended on, and where it is on the queue
+      v.init[slot] = init_word;
+      a.q_cursor[slot] = cur;
+    }
   };
 
   // ---- D on wave 1: lane l scatters part l / TILE of env l % TILE of the item in buffer p ----

@@ -3,8 +3,9 @@
 // Kernels: craft_tile.hip (tick / transition / observe / reset), craft_tick_lang.hip (the
 // language trainers' tick), craft_tick_stream.hip (the episode queue and its tick),
 // craft_tick_teach.hip (the tick fused with the teacher), craft_rollout_w3/w5/w7.hip (multi-tick),
-// craft_rollout_teach.hip (multi-tick with labels), craft_teacher.hip, craft_scenarios.hip (pool
-// generation).  Their launchers: craft_launch.h.
+// craft_rollout_teach.hip (multi-tick with labels), craft_rollout_stream.hip (multi-tick on the
+// episode queue), craft_teacher.hip, craft_scenarios.hip (pool generation).  Their launchers:
+// craft_launch.h.
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -14,6 +15,7 @@
 
 #include "craft_device.h"
 #include "craft_checks_lang_stream.h"
+#include "craft_checks_rollout_stream.h"
 #include "craft_host.h"
 #include "craft_launch.h"
 
@@ -1108,6 +1110,51 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
   if (captured) return CRAFT_OK;
   if (grid > 0 && split && !flat) s->queue1_next += (uint64_t)std::max<int64_t>(units, grid);
   else if (grid > 0) s->queue_next += (uint64_t)(units + grid);
+  return CRAFT_OK;
+}
+
+int craft_rollout_stream(craft_sim_t* s, const craft_rollout_stream_args_t* x, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  int rc = craft_host::check_rollout_stream(facts(s), x, s->last_error);
+  if (rc != CRAFT_OK) return rc;
+  if (x->n_ticks == 0) return CRAFT_OK;
+  craft::RolloutArgs a{};
+  a.actions = x->actions;
+  a.seed = x->action_seed;
+  a.tick0 = x->tick0;
+  a.n_ticks = x->n_ticks;
+  a.ring = x->ring;
+  a.flags = x->flags;
+  a.obs = x->obs;
+  a.reward = x->reward;
+  a.done = x->done;
+  a.sat = x->success;
+  a.chunk = x->n_ticks;                           // one unit per tile: all n_ticks ticks
+  a.q_entries = s->d_queue;
+  a.q_cursor = s->d_cursor;
+  a.q_count = (uint32_t)s->q_count;
+  a.q_step = s->q_step;
+  a.q_wrap = s->q_wrap;
+  a.ep_end = x->episode_end;
+  a.end_pose = x->end_pose;
+  a.ep_now = x->episode_now;
+  // 32-env tiles; 16 where craft_sim_tune says so or where 32 envs' two staged observation
+  // buffers exceed a workgroup's 160 KiB of LDS (the largest tile that fits)
+  const int tile = craft::rollout_stream_tile(s->k.tile_knob, s->view);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // the work-unit counter as craft_rollout's split kernel uses it (queue[1], one claim past the
+  // last unit per workgroup)
+  bool captured = false;
+  rc = rollout_sync(s, st, false, a, captured);
+  if (rc != CRAFT_OK) return rc;
+  int64_t grid = 0;
+  a.grid_out = &grid;
+  SimView view = s->view;
+  view.obs_policy = s->rollout_obs_policy;
+  const int64_t units = (s->n_envs + tile - 1) / tile;
+  const hipError_t e = craft::launch_rollout_stream(s->cfg.window_width, tile, view, a, st);
+  if (e != hipSuccess) return hip_fail(s, e, "craft_rollout_stream launch");
+  if (!captured && grid > 0) s->queue1_next += (uint64_t)std::max<int64_t>(units, grid);
   return CRAFT_OK;
 }
 

@@ -632,6 +632,152 @@ def _eval_summary(sim, specs, ids, rec, ended, pose, succ, ticks, lines):
                     is_get=is_get, end_pose=end_pose, ticks=ticks)
 
 
+class ReplayInfo:
+    """replay()'s results, host arrays in the order of `specs`: success int8 (satisfies() of the
+    state the episode ended in), length int32 (ticks the device ran the episode for), end_pose
+    int32 [count, 3] (x, y, dir of the final state); ticks and launches of the pass."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
+    """One pass over `specs` driven by recorded actions (a dataset's demonstrations, or the
+    `actions` of an EvalInfo), K ticks per launch on the episode queue (craft_rollout_stream):
+    the (state, action) pairs behaviour cloning trains on, without a launch per tick.
+
+    specs: as evaluate()'s.  action_seqs[e]: episode e's actions, each 0..5, at most
+      max_timesteps of them, ending in its only STOP or max_timesteps long; ValueError names the
+      first episode that is neither.  Under the imitation protocol such an episode takes exactly
+      len(action_seqs[e]) ticks, so slot i's action stream is the sequences of episodes i,
+      i + n, i + 2n, ... one after the other, and each launch's [K, n] action tensor is laid
+      out on the host.
+    on_chunk(obs, episode, step, action): called with [K, n, ...] device tensors, first with
+      the K = 1 chunk of begin_episodes' observations, then once per launch (the tensors are
+      overwritten by the next launch).  obs[k, i] is slot i's state after that tick, in the
+      simulator's obs format; episode (int32) the row of `specs` it belongs to, -1 for an idle
+      slot; step (int32) how many of that episode's actions were already taken; action (int32)
+      the recorded action taken next from that state, action_seqs[episode][step], or -1 for an
+      idle slot.  Over the pass the rows with action >= 0 are the (state, action) pairs of
+      every sequence, each exactly once.
+    Returns a ReplayInfo.  RolloutError if the device ran an episode for another number of ticks
+    than its sequence has, or latched an error."""
+    n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
+    K = int(ticks_per_launch)
+    if K < 1:
+        raise ValueError("ticks_per_launch must be >= 1")
+    if isinstance(specs, (tuple, list)) and len(specs) == 5 and np.ndim(specs[0]) == 1:
+        specs = np.stack([np.asarray(torch.as_tensor(a).cpu()) for a in specs], 1)
+    specs = np.ascontiguousarray(np.asarray(torch.as_tensor(specs).cpu()), dtype=np.int32)
+    if specs.ndim != 2 or specs.shape[1] != 5 or len(specs) == 0:
+        raise ValueError("specs must be [count >= 1, 5]")
+    count = len(specs)
+    if len(action_seqs) != count:
+        raise ValueError(f"{len(action_seqs)} action sequences for {count} specs")
+    seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in action_seqs]
+    for e, s in enumerate(seqs):
+        if len(s) > T:
+            raise ValueError(f"episode {e}: {len(s)} actions, max_timesteps is {T}")
+        if ((s < 0) | (s >= N.N_ACTIONS)).any():
+            raise ValueError(f"episode {e}: an action outside 0..{N.N_ACTIONS - 1}")
+        stops = np.nonzero(s == N.STOP)[0]
+        if len(stops) and stops[0] != len(s) - 1:
+            raise ValueError(f"episode {e}: STOP at step {int(stops[0])}, before its end")
+        if not len(stops) and len(s) != T:
+            raise ValueError(f"episode {e}: {len(s)} actions without a STOP (max_timesteps is {T})")
+    # every slot needs a first entry: a short split is padded with copies of its first row that
+    # STOP at once, whose episodes are dropped
+    pad = max(0, n - count)
+    queue = specs if not pad else np.concatenate([specs, np.repeat(specs[:1], pad, 0)])
+    seqs = seqs + [np.asarray([N.STOP], dtype=np.int64)] * pad
+    Q = len(queue)
+    length = np.asarray([len(s) for s in seqs], dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum(length)])[:-1]
+    flat = np.concatenate(seqs).astype(np.int32)
+    # ticks of the pass: the longest slot stream
+    per_slot = np.zeros(n, dtype=np.int64)
+    np.add.at(per_slot, np.arange(Q) % n, length)
+    total = int(per_slot.max())
+
+    sim.set_episode_queue(torch.as_tensor(queue))
+    obs0 = sim.empty_obs()
+    sim.begin_episodes(first=0, stride=n, wrap=False, obs=obs0)
+    i32 = dict(dtype=torch.int32, device=dev)
+    ring = torch.empty((K, n, sim.n_features), dtype=sim.obs_dtype, device=dev)
+    ended = torch.empty((K, n), **i32)
+    pose = torch.empty((K, n), **i32)
+    now = torch.empty((K, n), **i32)
+    succ = torch.empty((K, n), dtype=torch.int8, device=dev)
+
+    ep = np.arange(n, dtype=np.int64)                    # the episode each slot is on, -1: none left
+    st = np.zeros(n, dtype=np.int64)                     # actions of it already taken
+
+    def next_action(idle):
+        a = np.full(n, idle, dtype=np.int32)
+        on = ep >= 0
+        a[on] = flat[off[ep[on]] + st[on]]
+        return a
+
+    def shown(a):                                        # a padding episode's rows are nobody's pairs
+        return np.where(ep < count, a, -1).astype(np.int32)
+
+    if on_chunk is not None:
+        on_chunk(obs0[None], torch.as_tensor(shown(ep), **i32)[None], torch.zeros((1, n), **i32),
+                 torch.as_tensor(shown(next_action(-1)), **i32)[None])
+    success = np.full(count, -2, dtype=np.int8)
+    ran = np.full(count, -1, dtype=np.int32)
+    end_pose = np.zeros((count, 3), dtype=np.int32)
+    last_end = np.full(n, -1, dtype=np.int64)
+    t0 = launches = 0
+    while True:
+        k = min(K, total - t0)
+        if k <= 0:
+            raise RolloutError(f"replay: slots still running after {t0} ticks")
+        acts = np.zeros((k, n), dtype=np.int32)
+        c_st = np.empty((k, n), dtype=np.int32)
+        c_act = np.empty((k, n), dtype=np.int32)
+        for j in range(k):
+            acts[j] = next_action(0)                     # (an idle slot's action is ignored)
+            on = ep >= 0
+            st[on] += 1
+            over = on & (st == length[np.maximum(ep, 0)])
+            nxt = ep[over] + n
+            ep[over] = np.where(nxt < Q, nxt, -1)
+            st[over] = 0
+            c_st[j], c_act[j] = st, shown(next_action(-1))
+        # tick0 is a multiple of K, so tick t0 + j writes ring slot j
+        sim.rollout_stream(k, tick0=t0, actions=torch.as_tensor(acts).to(dev), obs=ring, success=succ,
+                           episode_end=ended, end_pose=pose, episode_now=now)
+        launches += 1
+        ee, pp, ss, nn = (x[:k].cpu().numpy() for x in (ended, pose, succ, now))
+        for j in range(k):
+            i = np.nonzero(ee[j] >= 0)[0]
+            e = ee[j, i]
+            keep = e < count
+            i, e = i[keep], e[keep]
+            ran[e] = t0 + j - last_end[i]
+            success[e] = ss[j, i]
+            p = pp[j, i]
+            end_pose[e] = np.stack([p & 0xff, (p >> 8) & 0xff, (p >> 16) & 3], 1)
+            last_end[np.nonzero(ee[j] >= 0)[0]] = t0 + j
+        if on_chunk is not None:
+            episode = torch.where(now[:k] >= count, -1, now[:k]).to(torch.int32)
+            on_chunk(ring[:k], episode, torch.as_tensor(c_st, **i32), torch.as_tensor(c_act, **i32))
+        t0 += k
+        if (nn[k - 1] < 0).all():
+            break
+    try:
+        sim.check()                                      # an error latched during the pass
+    except N.CraftError as e:
+        raise RolloutError(f"replay: {e}") from e
+    bad = np.nonzero(ran != length[:count])[0]
+    if len(bad):
+        e = int(bad[0])
+        raise RolloutError(f"replay: the device ran episode {e} for {int(ran[e])} ticks, "
+                           f"its sequence has {int(length[e])} actions")
+    return ReplayInfo(success=success, length=ran, end_pose=end_pose, ticks=t0, launches=launches)
+
+
 class ImitationRollout:
     """ImitationTrainer.do_rollout(batch, world, student, teacher, is_eval) over
     dataset batches (psketch_amd.dataset.Dataset items): one CraftSim per batch

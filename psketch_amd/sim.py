@@ -528,6 +528,40 @@ class CraftSim:
                 (_ptr(obs), int(ring or 1), _ptr(reward), _ptr(done), _ptr(success)))
         return obs
 
+    def rollout_stream(self, n_ticks, seed=0, tick0=0, actions=None, obs=None, reward=None,
+                       done=None, success=None, episode_end=None, end_pose=None, episode_now=None):
+        """n_ticks step_stream ticks in one launch (include/craft.h craft_rollout_stream),
+        identical to calling step_stream(tick=tick0 + k) n_ticks times: a slot whose episode
+        ends restarts on its next queue entry in the middle of the launch.  actions: int32
+        [n_ticks, N] or None (hashed); obs: [R, N, F] ring in the obs format (tick t writes
+        obs[t % R]); reward / done / success / episode_end / end_pose / episode_now: [R, N]
+        rings.  R is that of the first ring given."""
+        n = self.n_envs
+        if n_ticks < 0:
+            raise ValueError("n_ticks must be >= 0")
+        args = N.craft_rollout_stream_args_t()
+        keep = []
+        ring = _ring_extent((("obs", obs), ("reward", reward), ("done", done), ("success", success),
+                             ("episode_end", episode_end), ("end_pose", end_pose),
+                             ("episode_now", episode_now)), n) or 1
+        self._put_bufs(args, keep, (("obs", obs, self.obs_dtype, (ring, n, self.n_features)),
+                                    ("reward", reward, torch.float32, (ring, n)),
+                                    ("done", done, torch.uint8, (ring, n)),
+                                    ("success", success, torch.int8, (ring, n)),
+                                    ("episode_end", episode_end, torch.int32, (ring, n)),
+                                    ("end_pose", end_pose, torch.int32, (ring, n)),
+                                    ("episode_now", episode_now, torch.int32, (ring, n))))
+        if actions is not None:
+            _put(args, keep, "actions", self._i32(actions, n * n_ticks))
+        args.action_seed = seed & (2**64 - 1)
+        args.tick0 = int(tick0)
+        args.n_ticks = int(n_ticks)
+        args.flags = N.STEP_AUTORESET
+        args.ring = int(ring)
+        self._check(self._L.craft_rollout_stream(self._h, ctypes.byref(args), self._stream()),
+                    "craft_rollout_stream")
+        return obs
+
     def rollout_teach(self, n_ticks, seed=0, tick0=0, actions=None, autoreset=True, obs=None,
                       reward=None, done=None, success=None, labels=None, action_record=None,
                       label_in=None, behavior_clone=None, label_actions=False):

@@ -26,9 +26,22 @@ every side the same work instead: a given action buffer without STOP, so that wi
 window no episode ends on the lang side and, but for the tick on which every timer runs out at
 once, none restarts on the queued sides; the differences are then the modes' fixed costs.
 
+Two K-tick sides time the launches that keep a tile on chip between ticks: `rollout`
+(craft_rollout with CRAFT_STEP_AUTORESET: every slot replays its own spec) and `rollout_stream`
+(craft_rollout_stream, the same launch on the queue, wrap on); `rollout_split` is craft_rollout
+tuned to rollout_stream's launch shape (32-env tiles, 512 threads: the default at 3x3 windows
+only), so that at wider windows the queue's cost can be told from the shape's.  A timed run is `--launches`
+back-to-back launches of `--ticks` ticks each into an observation ring of `--ring` slots (the
+one-tick sides keep rewriting one buffer unless `--one-tick-ring` gives them the same ring, a
+slot per tick), microseconds per tick = time / (launches x ticks); they
+run without the teacher only.  rollout_stream - rollout is what the queue costs the K-tick launch
+(`--actions nostop`: no restart but the one tick on which every timer runs out, so the variant's
+fixed cost), rollout_stream - stream what the K-tick launch buys a queue workload.
+
     python tools/stream_bench.py [--envs 65536] [--steps 32] [--runs 9]
-                                 [--sides step,stream,lang,lang_stream] [--actions hashed|nostop]
-                                 [--tree DIR] [--out FILE]
+                                 [--sides step,stream,lang,lang_stream,rollout,rollout_split,rollout_stream]
+                                 [--actions hashed|nostop] [--ticks 20] [--launches 8] [--ring 16]
+                                 [--one-tick-ring] [--worlds w3,w5] [--tree DIR] [--out FILE]
 """
 import argparse
 import json
@@ -40,19 +53,38 @@ import numpy as np
 import torch
 
 
-QUEUED = ("stream", "lang_stream")
+QUEUED = ("stream", "lang_stream", "rollout_stream")
+KTICK = ("rollout", "rollout_split", "rollout_stream")
 
 
 def make(P, world, n, pool, specs, queue, side):
     sim = P.CraftSim(world, n_envs=n, device=0, pool_capacity=len(pool))
     sim.load_pool(pool)
     sim.tune_teach(kernel=1)
+    if side == "rollout_split":                  # craft_rollout in rollout_stream's launch shape
+        sim.tune(tile_envs=32, obs_store=2)
+        sim.tune_rollout(0, 512)
     if side in QUEUED:
         sim.set_episode_queue(torch.as_tensor(queue))
         sim.begin_episodes(wrap=True)
     else:
         sim.reset(*specs)
     return sim
+
+
+def timed_launches(sim, side, bufs, tick0, ticks, launches):
+    """A K-tick side: `launches` launches of `ticks` ticks, microseconds per tick."""
+    fn = sim.rollout_stream if side == "rollout_stream" else sim.rollout
+    kw = dict(seed=5, actions=bufs["ktick_actions"], obs=bufs["ring"])
+    fn(ticks, tick0=tick0, **kw)                                     # (warm)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for l in range(1, launches + 1):
+        fn(ticks, tick0=tick0 + l * ticks, **kw)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / (launches * ticks)
 
 
 def timed(sim, steps, side, bufs, tick0, specs):
@@ -71,7 +103,10 @@ def timed(sim, steps, side, bufs, tick0, specs):
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
+    ring = bufs.get("one_tick_ring")                                 # --one-tick-ring: tick t writes slot t % ring
     for t in range(tick0 + 1, tick0 + steps + 1):
+        if ring is not None:
+            kw["obs"] = ring[t % ring.shape[0]]
         fn(acts, seed=5, tick=t, **kw)
     e1.record()
     e1.synchronize()
@@ -85,6 +120,12 @@ def main():
     ap.add_argument("--runs", type=int, default=9)
     ap.add_argument("--sides", default="step,stream")
     ap.add_argument("--actions", default="hashed", choices=("hashed", "nostop"))
+    ap.add_argument("--ticks", type=int, default=20, help="ticks per launch of the K-tick sides")
+    ap.add_argument("--launches", type=int, default=8, help="launches per timed run of the K-tick sides")
+    ap.add_argument("--ring", type=int, default=16, help="observation ring slots of the K-tick sides")
+    ap.add_argument("--one-tick-ring", action="store_true",
+                    help="the one-tick sides write the K-tick sides' ring too, a slot per tick")
+    ap.add_argument("--worlds", default="w3,w5")
     ap.add_argument("--tree", default=None, help="checkout to import psketch_amd from (default: this one)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -94,11 +135,12 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("stream_bench needs a GPU")
     sides = [s for s in a.sides.split(",") if s]
-    if not set(sides) <= {"step", "stream", "lang", "lang_stream"}:
-        raise SystemExit("--sides: step, stream, lang, lang_stream")
+    if not set(sides) <= {"step", "stream", "lang", "lang_stream", "rollout", "rollout_split", "rollout_stream"}:
+        raise SystemExit("--sides: step, stream, lang, lang_stream, rollout, rollout_split, rollout_stream")
     n = a.envs
     lines = []
-    for world, W in (("craft_medium_12x12", 12), ("craft_medium_12x12_w5", 12)):
+    worlds = {"w3": ("craft_medium_12x12", 12), "w5": ("craft_medium_12x12_w5", 12)}
+    for world, W in (worlds[w] for w in a.worlds.split(",") if w):
         probe = P.CraftSim(world, n_envs=64, device=0, pool_capacity=1)
         if "lang" in sides and a.steps + 1 >= probe.config.max_timesteps:
             raise SystemExit("--steps must stay inside max_timesteps for the lang side")
@@ -111,17 +153,31 @@ def main():
         bufs = {"obs": next(iter(sims.values())).empty_obs(), "done": torch.empty(n, dtype=torch.uint8, device="cuda"),
                 "end": torch.empty(n, **i32), "pose": torch.empty(n, **i32), "now": torch.empty(n, **i32),
                 "actions": (torch.arange(n, **i32) % 5) if a.actions == "nostop" else None}
+        if set(sides) & set(KTICK):
+            bufs["ring"] = torch.empty((a.ring, n, bufs["obs"].shape[1]), dtype=bufs["obs"].dtype, device="cuda")
+            bufs["ktick_actions"] = (bufs["actions"].repeat(a.ticks, 1).contiguous()
+                                     if a.actions == "nostop" else None)
+            if a.one_tick_ring:
+                bufs["one_tick_ring"] = bufs["ring"]
         for teach in (False, True):
             bufs["labels"] = torch.empty(n, **i32) if teach else None
-            us = {k: [] for k in sims}
+            run_sides = [k for k in sims if not (teach and k in KTICK)]
+            if not run_sides:
+                continue
+            us = {k: [] for k in run_sides}
             for r in range(a.runs + 1):          # run 0 warms every side and is dropped
-                for k in sims:
-                    v = timed(sims[k], a.steps, k, bufs, r * (a.steps + 1), specs)
+                for k in run_sides:
+                    if k in KTICK:
+                        v = timed_launches(sims[k], k, bufs, r * (a.launches + 1) * a.ticks, a.ticks, a.launches)
+                    else:
+                        v = timed(sims[k], a.steps, k, bufs, r * (a.steps + 1), specs)
                     if r:
                         us[k].append(round(v, 3))
             for s in sims.values():
                 s.check()
             line = {"tree": tree, "world": world, "envs": n, "teacher": teach, "actions": a.actions, "steps": a.steps, "runs": a.runs,
+                    "ticks": a.ticks, "launches": a.launches, "ring": a.ring,
+                    "one_tick_ring": a.one_tick_ring,
                     "us_per_tick": us, "median_us": {k: statistics.median(v) for k, v in us.items()},
                     "spread_us": {k: round(max(v) - min(v), 3) for k, v in us.items()}}
             med = line["median_us"]
@@ -130,7 +186,9 @@ def main():
                 line["stream_minus_step_us"] = round(d, 3)
                 line["within_spread"] = abs(d) <= max(line["spread_us"].values())
             elif len(us) > 1:
-                for hi, lo in (("stream", "step"), ("lang_stream", "lang"), ("lang_stream", "stream")):
+                for hi, lo in (("stream", "step"), ("lang_stream", "lang"), ("lang_stream", "stream"),
+                               ("rollout_stream", "rollout"), ("rollout_stream", "rollout_split"),
+                               ("rollout_stream", "stream")):
                     if hi in med and lo in med:
                         line[f"{hi}_minus_{lo}_us"] = round(med[hi] - med[lo], 3)
             print(json.dumps(line), flush=True)
