@@ -592,6 +592,46 @@ typedef struct {
 } craft_rollout_teach_args_t;
 int craft_rollout_teach(craft_sim_t* sim, const craft_rollout_teach_args_t* args, void* stream);
 
+/* craft_rollout_teach on the episode queue: n_ticks consecutive craft_step_stream ticks (tick0,
+ * tick0 + 1, ...; label_out set) in one launch.  Tick k of that loop gets
+ *   step.actions        = actions[k], or NULL for the hashed draw;
+ *   step.ref_actions    = the labels the tick before produced (label_in for k = 0);
+ *   step.behavior_clone = behavior_clone, or all ones when label_actions, or NULL when labels
+ *                         feed no actions (neither is set),
+ * and the results are identical to those n_ticks calls: every ring row of every tick (obs in
+ * every format, reward, done, success, labels, action_record, episode_end, end_pose,
+ * episode_now), each slot's state, inventory, cleared cells, init pose and spec as
+ * craft_get_state reports them, its queue cursor, the craft_stats counters and the latched
+ * error.  A slot whose episode ends restarts on its next queue entry in the middle of the launch,
+ * any number of times.  The tick's label for a restarted slot is the teacher's answer for the new
+ * initial state under the new task, and that label is what the slot acts on next tick when it
+ * acts on labels; a slot that has run out freezes, with label -1.  It is what demonstration
+ * generation over a whole split (make_data.get_reference_actions, make_data.py:146-152,188-216;
+ * Python: rollout.demonstrations) and DAgger over fresh episodes (trainers/imitation.py:43-73 with
+ * CRAFT_QUEUE_WRAP) sit on.  The cursor is the one craft_step_stream, craft_step_lang_stream and
+ * craft_rollout_stream move, so a handle may mix all four between launches.  n_ticks == 0 is a
+ * no-op.
+ * CRAFT_EINVAL, tested in this order: teach.flags != CRAFT_STEP_AUTORESET; n_ticks < 0, ring < 1
+ * or tick0 < 0; the BFS-queue limit (4*W*H > 1000); label_actions or behavior_clone without
+ * label_in; an obs ring slot that is not 16-byte aligned; no craft_episode_begin since the queue
+ * was installed; and (the HIP library) a launch under stream capture while pool rows wait for
+ * their teacher-table entries (craft_sim_sync_table before capturing right after a pool load).
+ * Launch shape as craft_rollout_teach: 512 threads, one work unit per tile (32 envs at 3x3
+ * windows, 16 at wider ones) for the whole launch; craft_sim_tune_teach's table knob applies,
+ * observation stores are nontemporal unless craft_sim_tune set a policy.  Ordering and graph
+ * capture as craft_rollout_teach: the launches share craft_rollout's work-unit counter (one
+ * stream, or streams the caller orders), a captured launch uses the graph's own counter and the
+ * memset captured with it, and nothing is allocated on the step path.
+ * Measured against the per-tick craft_step_stream(label_out) loop and craft_rollout_teach:
+ * DESIGN.md "The teacher K-tick launch on the queue". */
+typedef struct {
+  craft_rollout_teach_args_t teach;  /* flags must be CRAFT_STEP_AUTORESET */
+  int32_t* episode_end;              /* [ring][n_envs], as craft_step_stream's */
+  int32_t* end_pose;
+  int32_t* episode_now;
+} craft_rollout_teach_stream_args_t;
+int craft_rollout_teach_stream(craft_sim_t* sim, const craft_rollout_teach_stream_args_t* args, void* stream);
+
 /* Sums the episode statistics accumulated by craft_step into stats_out
  * (device int64[3] = {successes, episodes ended, env-steps}) — the scalar
  * summary a multi-GPU run all-reduces over RCCL.  reset != 0 zeroes the

@@ -174,6 +174,15 @@ class craft_rollout_teach_args_t(ctypes.Structure):
     ]
 
 
+class craft_rollout_teach_stream_args_t(ctypes.Structure):
+    _fields_ = [
+        ("teach", craft_rollout_teach_args_t),
+        ("episode_end", ctypes.c_void_p),
+        ("end_pose", ctypes.c_void_p),
+        ("episode_now", ctypes.c_void_p),
+    ]
+
+
 OBS_F32, OBS_BF16, OBS_U8 = 0, 1, 2
 
 _vp = ctypes.c_void_p
@@ -221,6 +230,7 @@ SIGNATURES = {
     "craft_rollout": (_i32, [_vp, _vp, _u64, _i64, _i32, _u32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "craft_rollout_stream": (_i32, [_vp, ctypes.POINTER(craft_rollout_stream_args_t), _vp]),
     "craft_rollout_teach": (_i32, [_vp, ctypes.POINTER(craft_rollout_teach_args_t), _vp]),
+    "craft_rollout_teach_stream": (_i32, [_vp, ctypes.POINTER(craft_rollout_teach_stream_args_t), _vp]),
     "craft_stats": (_i32, [_vp, _vp, _i32, _vp]),
     "craft_transition": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "craft_observe": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),

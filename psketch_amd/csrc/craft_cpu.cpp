@@ -30,6 +30,7 @@
 
 #include "craft_checks_lang_stream.h"
 #include "craft_checks_rollout_stream.h"
+#include "craft_checks_rollout_teach_stream.h"
 #include "craft_host.h"
 
 namespace {
@@ -1331,6 +1332,44 @@ int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, voi
     in.label = lab.data();
     run_ticks(s, in, nullptr);
     if (x->labels) std::memcpy(x->labels + r * n, lab.data(), sizeof(int32_t) * n);
+    cur.swap(lab);
+  }
+  return CRAFT_OK;
+}
+
+// craft_rollout_teach_stream: the loop its contract names, each tick a craft_step_stream with the
+// teacher into its ring slot, acting (where a slot acts on labels) on the labels of the tick before
+int craft_rollout_teach_stream(craft_sim_t* s, const craft_rollout_teach_stream_args_t* x, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_rollout_teach_stream(facts(s), x, s->last_error)) return rc;
+  const craft_rollout_teach_args_t& p = x->teach;
+  const bool lsync = p.label_actions != 0 || p.behavior_clone != nullptr;
+  const int esz = craft_host::obs_elem_size(s->k.obs_fmt);
+  const int64_t n = s->n_envs;
+  std::vector<int32_t> cur(n, 0), lab(n, 0);
+  std::vector<uint8_t> ones;
+  if (p.label_actions) ones.assign((size_t)n, 1);
+  if (lsync) std::copy(p.label_in, p.label_in + n, cur.begin());
+  for (int32_t k = 0; k < p.n_ticks; ++k) {
+    const int64_t r = (p.tick0 + k) % p.ring;        // tick t writes ring slot t % ring
+    craft_stream_step_args_t t{};
+    t.step.actions = p.actions ? p.actions + (int64_t)k * n : nullptr;
+    t.step.ref_actions = lsync ? cur.data() : nullptr;
+    t.step.behavior_clone = p.label_actions ? ones.data() : p.behavior_clone;
+    t.step.action_seed = p.action_seed;
+    t.step.tick = p.tick0 + k;
+    t.step.flags = p.flags;
+    t.step.obs = p.obs ? static_cast<uint8_t*>(p.obs) + r * n * s->F * esz : nullptr;
+    t.step.reward = p.reward ? p.reward + r * n : nullptr;
+    t.step.done = p.done ? p.done + r * n : nullptr;
+    t.step.success = p.success ? p.success + r * n : nullptr;
+    t.step.action_record = p.action_record ? p.action_record + r * n : nullptr;
+    t.label_out = lab.data();
+    t.episode_end = x->episode_end ? x->episode_end + r * n : nullptr;
+    t.end_pose = x->end_pose ? x->end_pose + r * n : nullptr;
+    t.episode_now = x->episode_now ? x->episode_now + r * n : nullptr;
+    if (const int rc = craft_step_stream(s, &t, stream)) return rc;
+    if (p.labels) std::memcpy(p.labels + r * n, lab.data(), sizeof(int32_t) * n);
     cur.swap(lab);
   }
   return CRAFT_OK;

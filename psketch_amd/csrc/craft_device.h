@@ -265,7 +265,8 @@ struct RolloutArgs {       // craft_rollout: n_ticks ticks in one launch
   int32_t use_table;       // the teacher reads the teacher table for pristine grids
   int32_t* labels;         // [ring][n_envs] the label of every slot's new state, or null
   int32_t* rec;            // [ring][n_envs] the action taken (-1: none), or null
-  // craft_rollout_stream (rollout_split_kernel's QUEUE instantiations), appended so that the other
+  // craft_rollout_stream and craft_rollout_teach_stream (rollout_split_kernel's and
+  // rollout_teach_kernel's QUEUE instantiations), appended so that the other
   // kernels' argument words stay put: the packed queue, the cursors, the step and wrap rule as
   // TileArgs has them, and the tick's three extra outputs ([ring][n_envs] each, or null)
   const uint2* q_entries;

@@ -32,6 +32,8 @@ hipError_t launch_rollout(int win, int tile, int threads, const SimView& v, cons
 int rollout_stream_tile(int tile_knob, const SimView& v);
 hipError_t launch_rollout_stream(int win, int tile, const SimView& v, const RolloutArgs& a, hipStream_t st);
 hipError_t launch_rollout_teach(int win, int nw, const SimView& v, const RolloutArgs& a, hipStream_t st);
+// craft_rollout_teach_stream.hip: the same shape on the episode queue
+hipError_t launch_rollout_teach_stream(int win, int nw, const SimView& v, const RolloutArgs& a, hipStream_t st);
 // craft_teacher.hip
 hipError_t launch_teacher(int nw, int lanes, const SimView& v, const int32_t* slots, const int32_t* tasks,
                           int64_t n, int32_t* act_out, int32_t* len_out, hipStream_t st);

@@ -73,14 +73,16 @@ constexpr uint32_t kRtSpinCap = 1u << 22;
 // [2][up16(TILE*F)] | inventory rows [2][TILE][36] | agent words [2][TILE] | teacher info words
 // [2][TILE] | the tick's outputs [2][TILE][2] | task table [64] u16 | subtasks [64][4] | recipe
 // words [16][3] | control words [8] | label rows [8][4 + TILE] | BFS job queue [32][2 NW + 1] |
-// table requests [4][TILE] | their rows [4] | clearable cells [TILE][2] | hint table:
+// table requests [4][TILE] | their rows [4] | clearable cells [TILE][2] ([2][TILE][2] in the QUEUE
+// layout) | hint table:
 // descriptors [64][4], leaf bytes [2048] | nibble positions [4][TILE] | workshop recipes
 // [CRAFT_MAX_KINDS][4] uint2 (SimView::wsr) | the transition wave's labels [2][TILE]
 struct RtLds {
   int grid, pristine, obs, inv, agent, tinfo, cout, task, tsub, rc, ctrl, rows, jobs, treq, tval, tpend, tcell, hint,
       tnib, wsr, clab, bytes;
 };
-__host__ __device__ inline RtLds rt_lds(int tile, int GS, int F, int NW) {
+// (queue: rollout_teach_kernel's QUEUE layout, the listed clearable cells per item parity)
+__host__ __device__ inline RtLds rt_lds(int tile, int GS, int F, int NW, bool queue = false) {
   auto up16 = [](int x) { return (x + 15) & ~15; };
   RtLds l;
   l.tval = 0;                                              // [kRtLag][64] the words fetched (LDS-DMA)
@@ -100,7 +102,7 @@ __host__ __device__ inline RtLds rt_lds(int tile, int GS, int F, int NW) {
   l.treq = up16(l.jobs + kRtQueue * (2 * NW + 1) * 4);   // [kRtLag][tile] table-entry requests
   l.tpend = l.treq + kRtLag * tile * 4;                    // [kRtLag] their label rows (~0: none)
   l.tcell = l.tpend + kRtLag * 4;                          // [tile][2] each env's listed clearable cells
-  l.hint = up16(l.tcell + tile * 8);                       // craft_host.h hint_tables
+  l.hint = up16(l.tcell + (queue ? 2 : 1) * tile * 8);     // craft_host.h hint_tables
   l.tnib = l.hint + CRAFT_MAX_TASKS * 16 + craft_host::kHintLeafCap;   // [kRtLag][tile] nibble in the word
   l.wsr = up16(l.tnib + kRtLag * tile);
   l.clab = l.wsr + CRAFT_MAX_KINDS * 4 * 8;               // [2][tile] the transition wave's labels
@@ -160,7 +162,20 @@ __device__ __forceinline__ int rbyte(const uint32_t (&r)[8], int k) {
 // looking them up): it looks every lane's label up, cloning or not, publishes what it decodes,
 // and the teacher wave takes those instead of walking (a separate instantiation, so that the
 // policy launches keep their register allocation: the shared VGPR budget is tight).
-template <int WIN, int TILE, int NW, bool LA>
+//
+// QUEUE (craft_rollout_teach_stream).  The same pipeline on the episode queue, as
+// rollout_split_kernel's QUEUE path (craft_rollout_split.h): a slot whose episode ends takes its
+// next queue entry, fetched an episode ahead, and wave 0 reloads its pristine row and the item's
+// grid row from pool[scenario] in the middle of the unit (kReload: the next C copies the whole row
+// to the other parity buffer), or freezes it when the queue has none.  What load_tile sets once
+// per tile then changes with the entry: the task word, the row's connectivity bit, the hint
+// descriptor, the row's listed clearable cells and the cleared-cell count and list.  The teacher
+// wave reads all of an item's per-env words by the item's parity (s_agent, s_tinfo and, in this
+// layout only, s_tcell), so a reload in C(i+1) never changes what T(i) reads; its BFS jobs copy
+// their band bitsets out of buffer i & 1 inside interval i, and its table requests carry their own
+// row and index.  episode_end / end_pose / episode_now leave from wave 0; the unit's end also
+// publishes the init word and the cursor.
+template <int WIN, int TILE, int NW, bool LA, bool QUEUE = false>
 __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v, RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int NT = kRtThreads, NWAVE = NT / 64, TW = NWAVE - 1;   // the teacher is the last wave
@@ -171,7 +186,7 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
   static_assert(TILE <= 32 && 64 % TILE == 0, "the teacher's walk: one lane per env");
   auto up16 = [](int x) { return (x + 15) & ~15; };
   const int GS = v.GS, F = v.F, H = v.H, C = v.C;
-  const RtLds lay = rt_lds(TILE, GS, F, NW);
+  const RtLds lay = rt_lds(TILE, GS, F, NW, QUEUE);
   // the recipe words in a VGPR (lane w: word w), loaded while every lane is active (v_readlane)
   const uint32_t rcv = v.rcw[min((int)(threadIdx.x & 63), CRAFT_MAX_RECIPES * 3 - 1)];
   uint8_t* s_grid = smem + lay.grid;                                  // [2][TILE][GS] by item parity
@@ -187,7 +202,8 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
   uint32_t* s_treq = reinterpret_cast<uint32_t*>(smem + lay.treq);    // [kRtLag][TILE] ttab index, ~0 = none
   uint32_t* s_tval = reinterpret_cast<uint32_t*>(smem + lay.tval);    // [kRtLag][64] fetched table words
   uint32_t* s_tpend = reinterpret_cast<uint32_t*>(smem + lay.tpend);  // [kRtLag] their label rows, ~0 none
-  uint32_t* s_tcell = reinterpret_cast<uint32_t*>(smem + lay.tcell);  // [TILE][2] tt_cells of the env's row
+  // [TILE][2] tt_cells of the env's row (QUEUE: [2][TILE][2] by item parity, as s_tinfo)
+  uint32_t* s_tcell = reinterpret_cast<uint32_t*>(smem + lay.tcell);
   uint8_t* s_tnib = smem + lay.tnib;                                  // [kRtLag][TILE] the answer's nibble
   uint16_t* s_task = reinterpret_cast<uint16_t*>(smem + lay.task);
   int32_t* s_tsub = reinterpret_cast<int32_t*>(smem + lay.tsub);
@@ -285,6 +301,9 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
     uint32_t chg = 0;
     uint32_t clk = 0, clk_prev = 0;   // the kinds of clr's (up to 3) cells before they were cleared
     constexpr uint32_t kRestart = 0x80000000u;
+    constexpr uint32_t kReload = 0x40000000u;   // QUEUE: the row was reloaded from another pool row
+    int32_t cur = -1;                  // QUEUE: the slot's queue cursor (craft_episode.h)
+    uint2 qe = make_uint2(0u, 0u);     // and the entry after it, fetched an episode ahead
     int sync = 0, lab0 = 0;
     // (label actions) the label of the state the last tick made, looked up by this wave itself:
     // a label byte, kCNib | the nibble's position in c_word (the nibble table's dword, loaded at
@@ -328,11 +347,16 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
       if (live) {
         st = v.state[slot];
         init_word = v.init[slot];
+        if constexpr (QUEUE) cur = a.q_cursor[slot];
         const uint4 i0 = v.inv[2 * slot], i1 = v.inv[2 * slot + 1];
         const uint4 m0 = v.mask[2 * slot], m1 = v.mask[2 * slot + 1];
         uint32_t bcw = 0;
         if (a.bc) bcw = a.bc[slot];
         if (lsync) lab0 = a.label_in[slot];
+        if constexpr (QUEUE) {                                         // (last: it waits for the cursor)
+          const int32_t nxt = queue_next(cur, a.q_count, a.q_step, a.q_wrap);
+          if (nxt >= 0) qe = a.q_entries[nxt];
+        }
         ivr[0] = i0.x; ivr[1] = i0.y; ivr[2] = i0.z; ivr[3] = i0.w;
         ivr[4] = i1.x; ivr[5] = i1.y; ivr[6] = i1.z; ivr[7] = i1.w;
         m[0] = m0.x; m[1] = m0.y; m[2] = m0.z; m[3] = m0.w;
@@ -355,8 +379,12 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
         conn = v.pool_conn[s.scen];
         if (v.ttab) {                                                  // the row's clearable cells the table lists
           c_cw = make_uint2(v.tt_cells[2 * (size_t)s.scen], v.tt_cells[2 * (size_t)s.scen + 1]);
-          s_tcell[2 * lane] = c_cw.x;
-          s_tcell[2 * lane + 1] = c_cw.y;
+          if constexpr (!QUEUE) {                                      // (QUEUE: every tick_c, by parity)
+            s_tcell[2 * lane] = c_cw.x;
+            s_tcell[2 * lane + 1] = c_cw.y;
+          }
+        } else if constexpr (QUEUE) {
+          c_cw = make_uint2(~0u, ~0u);
         }
         if (lsync) {
           const uint4 hd = s_hdesc[s.task];
@@ -490,7 +518,7 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
       s = unpack_state(st);
       const uint64_t tc0 = RT_CLK();
       if (live) {
-        if (sync == 1) {                                               // bring the buffer up to date
+        if (sync == 1 || (QUEUE && chg == kReload)) {                  // bring the buffer up to date
           copy_row_words(reinterpret_cast<uint32_t*>(gr), reinterpret_cast<const uint32_t*>(grid_of(k + 1)), v.CS);
         } else if (sync == 2) {
           if (chg == kRestart) restore(gr, clr_prev, clk_prev);
@@ -512,7 +540,41 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
           succ = satisfies_with(
               task_word, [&](int arg) __attribute__((always_inline)) { return rbyte(ivn, arg); },
               [&]() __attribute__((always_inline)) { return (int)gr[facing_cell(s, H)]; });
-        if (restart) {
+        int32_t ended = -1, epose = -1;                                // QUEUE: the tick's episode_end and end_pose
+        if constexpr (QUEUE) {
+          if (restart) {
+            // the slot's next episode, as tile_kernel's MODE_STREAM takes it: the entry's scenario,
+            // pose and task, an empty inventory, nothing cleared, pool[scenario] as the pristine
+            // row and this item's grid row, and the teacher's per-slot words of the new row and
+            // task; without a next entry the slot freezes and its cursor becomes -1
+            ended = cur;
+            epose = (int32_t)pose_word(s);
+            cur = queue_next(cur, a.q_count, a.q_step, a.q_wrap);
+            if (cur >= 0) {
+              restart_from_entry(s, qe, v.maxT);
+              task_word = s_task[s.task];
+              init_word = qe.y;
+              conn = v.pool_conn[s.scen];
+              if (v.ttab) c_cw = make_uint2(v.tt_cells[2 * (size_t)s.scen], v.tt_cells[2 * (size_t)s.scen + 1]);
+              if (lsync) {
+                const uint4 hd = s_hdesc[s.task];
+                c_hd = make_uint3(hd.x, hd.y, hd.z);
+              }
+#pragma unroll
+              for (int w = 0; w < 8; ++w) reinterpret_cast<uint32_t*>(iv)[w] = 0u;
+              load_pool_row(reinterpret_cast<const uint4*>(v.pool + (size_t)s.scen * v.CS),
+                            reinterpret_cast<uint32_t*>(s_pristine + lane * GS), reinterpret_cast<uint32_t*>(gr), v.CS);
+              clr.clear();
+              clk = 0;
+              chg = kReload;
+              ncl = 0;
+              const int32_t nxt = queue_next(cur, a.q_count, a.q_step, a.q_wrap);
+              if (nxt >= 0) qe = a.q_entries[nxt];                     // (behind the row's loads: nothing waits for it here)
+            } else {
+              freeze_agent(s);
+            }
+          }
+        } else if (restart) {
           restart_agent(s, init_word, v.maxT);
 #pragma unroll
           for (int w = 0; w < 8; ++w) reinterpret_cast<uint32_t*>(iv)[w] = 0u;
@@ -543,6 +605,12 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
           }
         }
         st = pack_state(s);
+        if constexpr (QUEUE) {
+          const int64_t o = (tick % a.ring) * n + slot;
+          if (a.ep_end) a.ep_end[o] = ended;
+          if (a.end_pose) a.end_pose[o] = epose;
+          if (a.ep_now) a.ep_now[o] = s.frozen ? -1 : cur;
+        }
         RT_ACC(3, tc2);
         const uint64_t tc3 = RT_CLK();
 #pragma unroll
@@ -562,6 +630,10 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
         s_agent[(k & 1) * TILE + lane] =
             live ? (agent_word(s, true) | ((uint32_t)s.frozen << 25) | ((uint32_t)min(ncl, 63) << 26)) : 0u;
         s_tinfo[(k & 1) * TILE + lane] = (uint32_t)s.task | (conn << 8) | ((uint32_t)s.scen << 10);
+        if constexpr (QUEUE) {
+          s_tcell[2 * ((k & 1) * TILE + lane)] = c_cw.x;
+          s_tcell[2 * ((k & 1) * TILE + lane) + 1] = c_cw.y;
+        }
       }
     };
     // ---- the tile's state back to HBM from buffer p (the mask rebuilt from the rows) ----
@@ -569,6 +641,10 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
       uint32_t m[8];
       cleared_mask(pw, reinterpret_cast<const uint32_t*>(grid_of(p)), C, m);
       publish_state(v, slot, st, reinterpret_cast<const uint32_t*>(inv_of(p)), m, false);
+      if constexpr (QUEUE) {                            // the spec the slot ended on, and where it is on the queue
+        v.init[slot] = init_word;
+        a.q_cursor[slot] = cur;
+      }
     };
     bool first = (uint32_t)blockIdx.x < n_units;
     uint32_t gbase = 0;
@@ -1051,7 +1127,8 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
             // and the listed cells' kinds now; the hint leaf
             const uint32_t ag = s_agent[p * TILE + lane];
             const uint32_t ti = s_tinfo[p * TILE + lane];
-            const uint32_t cw0 = s_tcell[2 * lane], cw1 = s_tcell[2 * lane + 1];
+            const int tcl = QUEUE ? p * TILE + lane : lane;
+            const uint32_t cw0 = s_tcell[2 * tcl], cw1 = s_tcell[2 * tcl + 1];
             const bool live_env = (ag >> 24) & 1u;
             const int x = ag & 0xff, y = (ag >> 8) & 0xff, dir = (ag >> 16) & 3;
             const uint8_t* gr = s_grid + p * TILE * GS + lane * GS;

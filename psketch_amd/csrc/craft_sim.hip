@@ -4,7 +4,7 @@
 // language trainers' tick), craft_tick_stream.hip (the episode queue and its tick),
 // craft_tick_teach.hip (the tick fused with the teacher), craft_rollout_w3/w5/w7.hip (multi-tick),
 // craft_rollout_teach.hip (multi-tick with labels), craft_rollout_stream.hip (multi-tick on the
-// episode queue), craft_teacher.hip, craft_scenarios.hip (pool generation).  Their launchers:
+// episode queue), craft_rollout_teach_stream.hip (both), craft_teacher.hip, craft_scenarios.hip (pool generation).  Their launchers:
 // craft_launch.h.
 #include <algorithm>
 #include <cstdlib>
@@ -16,6 +16,7 @@
 #include "craft_device.h"
 #include "craft_checks_lang_stream.h"
 #include "craft_checks_rollout_stream.h"
+#include "craft_checks_rollout_teach_stream.h"
 #include "craft_host.h"
 #include "craft_launch.h"
 
@@ -1202,6 +1203,60 @@ int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, voi
   const int64_t units = (s->n_envs + craft::rt_tile_of(s->cfg.window_width) - 1) / craft::rt_tile_of(s->cfg.window_width);
   hipError_t e = craft::launch_rollout_teach(s->cfg.window_width, craft::teach_words(s->view.W, s->view.H), v, a, st);
   if (e != hipSuccess) return hip_fail(s, e, "craft_rollout_teach launch");
+  if (!captured && grid > 0) s->queue1_next += (uint64_t)std::max<int64_t>(units, grid);
+  return CRAFT_OK;
+}
+
+int craft_rollout_teach_stream(craft_sim_t* s, const craft_rollout_teach_stream_args_t* x, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  int rc = craft_host::check_rollout_teach_stream(facts(s), x, s->last_error);
+  if (rc != CRAFT_OK) return rc;
+  const craft_rollout_teach_args_t& t = x->teach;
+  if (t.n_ticks == 0) return CRAFT_OK;
+  const bool lsync = t.label_actions != 0 || t.behavior_clone != nullptr;
+  craft::RolloutArgs a{};
+  a.actions = t.actions;
+  a.seed = t.action_seed;
+  a.tick0 = t.tick0;
+  a.n_ticks = t.n_ticks;
+  a.ring = t.ring;
+  a.flags = t.flags;
+  a.obs = t.obs;
+  a.reward = t.reward;
+  a.done = t.done;
+  a.sat = t.success;
+  a.chunk = t.n_ticks;                            // one unit per tile: all n_ticks ticks
+  a.label_in = t.label_in;
+  a.bc = t.behavior_clone;
+  a.label_actions = t.label_actions != 0;
+  a.lsync = lsync ? (s->hint_walk ? 1 : 2) : 0;     // as craft_rollout_teach
+  a.use_table = s->k.teach_table != 2;
+  a.labels = t.labels;
+  a.rec = t.action_record;
+  a.q_entries = s->d_queue;
+  a.q_cursor = s->d_cursor;
+  a.q_count = (uint32_t)s->q_count;
+  a.q_step = s->q_step;
+  a.q_wrap = s->q_wrap;
+  a.ep_end = x->episode_end;
+  a.end_pose = x->end_pose;
+  a.ep_now = x->episode_now;
+  rc = flush_table(s, stream, "craft_rollout_teach_stream");
+  if (rc != CRAFT_OK) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // the work-unit counter as craft_rollout_teach uses it (queue[1], one claim past the last unit
+  // per workgroup)
+  bool captured = false;
+  rc = rollout_sync(s, st, false, a, captured);
+  if (rc != CRAFT_OK) return rc;
+  int64_t grid = 0;
+  a.grid_out = &grid;
+  SimView v = teach_view(s);
+  v.obs_policy = s->obs_store_tuned ? s->rollout_obs_policy : 1;   // nontemporal unless tuned (craft_rollout_teach)
+  const int tile = craft::rt_tile_of(s->cfg.window_width);
+  const int64_t units = (s->n_envs + tile - 1) / tile;
+  const hipError_t e = craft::launch_rollout_teach_stream(s->cfg.window_width, craft::teach_words(s->view.W, s->view.H), v, a, st);
+  if (e != hipSuccess) return hip_fail(s, e, "craft_rollout_teach_stream launch");
   if (!captured && grid > 0) s->queue1_next += (uint64_t)std::max<int64_t>(units, grid);
   return CRAFT_OK;
 }

@@ -778,6 +778,123 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
     return ReplayInfo(success=success, length=ran, end_pose=end_pose, ticks=t0, launches=launches)
 
 
+class DemonstrationInfo:
+    """demonstrations()'s results, host arrays in the order of `specs`: action_seqs int32
+    [count, max_timesteps] (each episode's actions, its STOP included, padded with -1), length
+    int32, success int8 (satisfies() of the state the episode ended in), end_pose int32
+    [count, 3] (x, y, dir of the final state); ticks and launches of the pass."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def actions(self, e):
+        """Episode e's action sequence as a list of ints."""
+        return [int(a) for a in self.action_seqs[e, :self.length[e]]]
+
+
+def demonstrations(sim, specs, ticks_per_launch=32):
+    """make_data.get_reference_actions (make_data.py:146-152) for a whole list of (scenario,
+    start, task) instances in one pass over the episode queue: every slot acts on the teacher's
+    label of its current state until the label is STOP, then takes its next instance, K ticks
+    per launch (craft_rollout_teach_stream with label_actions).
+
+    specs: as evaluate()'s.  Returns a DemonstrationInfo.  RolloutError names the first instance
+    for which the teacher raised, whose episode reached the time limit without a STOP, or whose
+    episode ended with its task unsatisfied (the reference's assert state.satisfies(task))."""
+    n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
+    K = int(ticks_per_launch)
+    if K < 1:
+        raise ValueError("ticks_per_launch must be >= 1")
+    if isinstance(specs, (tuple, list)) and len(specs) == 5 and np.ndim(specs[0]) == 1:
+        specs = np.stack([np.asarray(torch.as_tensor(a).cpu()) for a in specs], 1)
+    specs = np.ascontiguousarray(np.asarray(torch.as_tensor(specs).cpu()), dtype=np.int32)
+    if specs.ndim != 2 or specs.shape[1] != 5 or len(specs) == 0:
+        raise ValueError("specs must be [count >= 1, 5]")
+    count = len(specs)
+    # every slot needs a first entry: a short list is padded with copies of its first row, whose
+    # episodes are dropped
+    pad = max(0, n - count)
+    queue = specs if not pad else np.concatenate([specs, np.repeat(specs[:1], pad, 0)])
+    Q = len(queue)
+    bound = -(-Q // n) * T                                # no slot's stream of episodes is longer
+
+    sim.set_episode_queue(torch.as_tensor(queue))
+    sim.begin_episodes(first=0, stride=n, wrap=False)
+    label_in, _ = sim.teacher()
+    i32 = dict(dtype=torch.int32, device=dev)
+    labels = torch.empty((K, n), **i32)
+    rec = torch.empty((K, n), **i32)
+    ended = torch.empty((K, n), **i32)
+    pose = torch.empty((K, n), **i32)
+    now = torch.empty((K, n), **i32)
+    succ = torch.empty((K, n), dtype=torch.int8, device=dev)
+    rows = {k: [] for k in ("rec", "ended", "pose", "succ", "now", "labels")}
+    raised = np.nonzero(label_in.cpu().numpy() == -2)[0]  # (slot i starts on instance i)
+    raised = raised[raised < count]
+    first_raise = int(raised[0]) if len(raised) else None
+    t0 = launches = 0
+    while True:
+        if t0 >= bound:
+            raise RolloutError(f"demonstrations: slots still running after {t0} ticks")
+        # tick0 is a multiple of K, so tick t0 + j writes ring slot j
+        sim.rollout_teach_stream(K, tick0=t0, label_actions=True, label_in=label_in, labels=labels,
+                                 action_record=rec, success=succ, episode_end=ended, end_pose=pose,
+                                 episode_now=now)
+        launches += 1
+        label_in = labels[K - 1].clone()
+        for k, x in (("rec", rec), ("ended", ended), ("pose", pose), ("succ", succ), ("now", now),
+                     ("labels", labels)):
+            rows[k].append(x.cpu().numpy().copy())
+        t0 += K
+        if (rows["now"][-1][K - 1] < 0).all():
+            break
+    rec, ended, pose, succ, now, labels = (np.concatenate(rows[k]) for k in
+                                           ("rec", "ended", "pose", "succ", "now", "labels"))
+    bad = (labels == -2) & (now >= 0) & (now < count)
+    if bad.any():
+        e = int(now[bad].min())
+        first_raise = e if first_raise is None else min(e, first_raise)
+    try:
+        sim.check()                                      # an error latched during the pass
+    except N.CraftError as e:
+        if first_raise is None:
+            raise RolloutError(f"demonstrations: {e}") from e
+    if first_raise is not None:
+        raise RolloutError(f"demonstrations: the teacher raised on instance {first_raise}")
+
+    seqs = np.full((count, T), -1, dtype=np.int32)
+    length = np.zeros(count, dtype=np.int32)
+    success = np.full(count, -2, dtype=np.int8)          # -2: never finished
+    end_pose = np.zeros((count, 3), dtype=np.int32)
+    stopped = np.zeros(count, dtype=bool)
+    # slot i runs instances i, i + n, ... in order: cut its action column at its episode ends
+    tt, ii = np.nonzero(ended >= 0)
+    start = np.zeros(n, dtype=np.int64)
+    for t, i in zip(tt, ii):                             # (np.nonzero: tick-major, so in order per slot)
+        e = ended[t, i]
+        if e < count:
+            a = rec[start[i]:t + 1, i]
+            seqs[e, :len(a)] = a
+            length[e] = len(a)
+            success[e] = succ[t, i]
+            stopped[e] = a[-1] == N.STOP
+            p = pose[t, i]
+            end_pose[e] = (p & 0xff, (p >> 8) & 0xff, (p >> 16) & 3)
+        start[i] = t + 1
+    if (success == -2).any():
+        raise RolloutError(f"demonstrations: instance {int(np.argmax(success == -2))} was never finished")
+    wrong = ~stopped | (success != 1)
+    if wrong.any():
+        e = int(np.argmax(wrong))
+        if not stopped[e]:
+            raise RolloutError(f"demonstrations: instance {e} reached the time limit "
+                               f"({T} steps) without a STOP")
+        raise RolloutError(f"demonstrations: instance {e} ended with its task unsatisfied "
+                           f"(satisfies() = {int(success[e])})")
+    return DemonstrationInfo(action_seqs=seqs, length=length, success=success, end_pose=end_pose,
+                             ticks=t0, launches=launches)
+
+
 class ImitationRollout:
     """ImitationTrainer.do_rollout(batch, world, student, teacher, is_eval) over
     dataset batches (psketch_amd.dataset.Dataset items): one CraftSim per batch

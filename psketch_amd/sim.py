@@ -621,6 +621,54 @@ class CraftSim:
                                  self._ring_sig(*outs_t), args)
         return labels
 
+    def rollout_teach_stream(self, n_ticks, seed=0, tick0=0, actions=None, obs=None, reward=None,
+                             done=None, success=None, labels=None, action_record=None,
+                             label_in=None, behavior_clone=None, label_actions=False,
+                             episode_end=None, end_pose=None, episode_now=None):
+        """n_ticks step_stream(..., labels=) ticks in one launch (include/craft.h
+        craft_rollout_teach_stream): rollout_teach on the episode queue.  A slot whose episode
+        ends restarts on its next queue entry in the middle of the launch; its label that tick
+        is the teacher's answer for the new initial state and task, which it acts on next tick
+        when it acts on labels (label_actions: every slot; behavior_clone[i]: uint8 [N]).
+        Otherwise actions[k] (int32 [n_ticks, N]) or the hashed draw.  label_in (int32 [N]): the
+        labels of the states before tick0, needed when labels feed actions.  Outputs are [R, ...]
+        rings (tick t writes slot t % R): rollout_teach's six and rollout_stream's episode_end,
+        end_pose and episode_now (int32)."""
+        n = self.n_envs
+        if n_ticks < 0:
+            raise ValueError("n_ticks must be >= 0")
+        args = N.craft_rollout_teach_stream_args_t()
+        t = args.teach
+        keep = []
+        ring = _ring_extent((("obs", obs), ("reward", reward), ("done", done), ("success", success),
+                             ("labels", labels), ("action_record", action_record),
+                             ("episode_end", episode_end), ("end_pose", end_pose),
+                             ("episode_now", episode_now)), n) or 1
+        self._put_bufs(t, keep, (("obs", obs, self.obs_dtype, (ring, n, self.n_features)),
+                                 ("reward", reward, torch.float32, (ring, n)),
+                                 ("done", done, torch.uint8, (ring, n)),
+                                 ("success", success, torch.int8, (ring, n)),
+                                 ("labels", labels, torch.int32, (ring, n)),
+                                 ("action_record", action_record, torch.int32, (ring, n))))
+        self._put_bufs(args, keep, (("episode_end", episode_end, torch.int32, (ring, n)),
+                                    ("end_pose", end_pose, torch.int32, (ring, n)),
+                                    ("episode_now", episode_now, torch.int32, (ring, n))))
+        if actions is not None:
+            _put(t, keep, "actions", self._i32(actions, n * n_ticks))
+        if label_in is not None:
+            _put(t, keep, "label_in", self._i32(label_in, n))
+        if behavior_clone is not None:
+            _put(t, keep, "behavior_clone", self._flag_mask("behavior_clone", behavior_clone, n))
+        t.label_actions = 1 if label_actions else 0
+        t.action_seed = seed & (2**64 - 1)
+        t.tick0 = int(tick0)
+        t.n_ticks = int(n_ticks)
+        t.flags = N.STEP_AUTORESET
+        t.ring = int(ring)
+        self._check(self._L.craft_rollout_teach_stream(self._h, ctypes.byref(args), self._stream()),
+                    "craft_rollout_teach_stream")
+        return labels
+
     @staticmethod
     def _ring_sig(*ts):
         """Storage, shape, strides, dtype and device of each output ring (a tensor resized,

@@ -38,9 +38,20 @@ run without the teacher only.  rollout_stream - rollout is what the queue costs 
 (`--actions nostop`: no restart but the one tick on which every timer runs out, so the variant's
 fixed cost), rollout_stream - stream what the K-tick launch buys a queue workload.
 
+Two more K-tick sides carry the teacher: `rollout_teach` (craft_rollout_teach, every slot on its own
+spec) and `rollout_teach_stream` (craft_rollout_teach_stream, the same launch on the queue, wrap
+on).  They run in the teacher pass only, writing the observation ring and a labels ring, beside the
+`stream` side's per-tick craft_step_stream(label_out) (give it the ring with --one-tick-ring).
+rollout_teach_stream - rollout_teach is what the queue costs the launch, rollout_teach_stream -
+stream what the launch buys a queue workload.  `--actions label` makes every slot act on its label
+(make_data's demonstrations): the K-tick sides with label_actions, each launch fed the labels of
+the tick before it, the stream side with ref_actions = the last tick's labels and behavior_clone
+all ones; only these three sides take it.
+
     python tools/stream_bench.py [--envs 65536] [--steps 32] [--runs 9]
-                                 [--sides step,stream,lang,lang_stream,rollout,rollout_split,rollout_stream]
-                                 [--actions hashed|nostop] [--ticks 20] [--launches 8] [--ring 16]
+                                 [--sides step,stream,lang,lang_stream,rollout,rollout_split,rollout_stream,
+                                          rollout_teach,rollout_teach_stream]
+                                 [--actions hashed|nostop|label] [--ticks 20] [--launches 8] [--ring 16]
                                  [--one-tick-ring] [--worlds w3,w5] [--tree DIR] [--out FILE]
 """
 import argparse
@@ -53,8 +64,10 @@ import numpy as np
 import torch
 
 
-QUEUED = ("stream", "lang_stream", "rollout_stream")
+QUEUED = ("stream", "lang_stream", "rollout_stream", "rollout_teach_stream")
 KTICK = ("rollout", "rollout_split", "rollout_stream")
+KTICK_TEACH = ("rollout_teach", "rollout_teach_stream")
+ALL_SIDES = ("step", "stream", "lang", "lang_stream") + KTICK + KTICK_TEACH
 
 
 def make(P, world, n, pool, specs, queue, side):
@@ -85,6 +98,56 @@ def timed_launches(sim, side, bufs, tick0, ticks, launches):
     e1.record()
     e1.synchronize()
     return e0.elapsed_time(e1) * 1e3 / (launches * ticks)
+
+
+def timed_teach_launches(sim, side, bufs, tick0, ticks, launches, label):
+    """A teacher K-tick side: `launches` launches of `ticks` ticks into the observation and labels
+    rings, microseconds per tick.  label: every slot acts on its label, each launch fed the last
+    labels the launch before it wrote (a copy into label_in: the ring slot is rewritten)."""
+    fn = sim.rollout_teach_stream if side == "rollout_teach_stream" else sim.rollout_teach
+    ring = bufs["label_ring"]
+    kw = dict(seed=5, actions=bufs["ktick_actions"], obs=bufs["ring"], labels=ring)
+    cur = bufs["label_in"]
+    if label:
+        cur.copy_(sim.teacher()[0])
+        kw.update(label_actions=True, label_in=cur)
+
+    def launch(t0):
+        fn(ticks, tick0=t0, **kw)
+        if label:
+            cur.copy_(ring[(t0 + ticks - 1) % ring.shape[0]])
+    launch(tick0)                                                    # (warm)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for l in range(1, launches + 1):
+        launch(tick0 + l * ticks)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / (launches * ticks)
+
+
+def timed_label_stream(sim, steps, bufs, tick0):
+    """The stream side under --actions label: craft_step_stream(label_out) per tick, every slot
+    acting on the labels of the tick before, labels into the ring's slot of the tick."""
+    ring, obs_ring = bufs["label_ring"], bufs.get("one_tick_ring")
+    R = ring.shape[0]
+    kw = dict(done=bufs["done"], behavior_clone=bufs["ones"], episode_end=bufs["end"], end_pose=bufs["pose"],
+              episode_now=bufs["now"])
+    ring[(tick0 - 1) % R].copy_(sim.teacher()[0])
+
+    def tick(t):
+        sim.step_stream(None, seed=5, tick=t, obs=bufs["obs"] if obs_ring is None else obs_ring[t % obs_ring.shape[0]],
+                        ref_actions=ring[(t - 1) % R], labels=ring[t % R], **kw)
+    tick(tick0)                                                      # (warm)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for t in range(tick0 + 1, tick0 + steps + 1):
+        tick(t)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / steps
 
 
 def timed(sim, steps, side, bufs, tick0, specs):
@@ -119,7 +182,7 @@ def main():
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--runs", type=int, default=9)
     ap.add_argument("--sides", default="step,stream")
-    ap.add_argument("--actions", default="hashed", choices=("hashed", "nostop"))
+    ap.add_argument("--actions", default="hashed", choices=("hashed", "nostop", "label"))
     ap.add_argument("--ticks", type=int, default=20, help="ticks per launch of the K-tick sides")
     ap.add_argument("--launches", type=int, default=8, help="launches per timed run of the K-tick sides")
     ap.add_argument("--ring", type=int, default=16, help="observation ring slots of the K-tick sides")
@@ -135,8 +198,11 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("stream_bench needs a GPU")
     sides = [s for s in a.sides.split(",") if s]
-    if not set(sides) <= {"step", "stream", "lang", "lang_stream", "rollout", "rollout_split", "rollout_stream"}:
-        raise SystemExit("--sides: step, stream, lang, lang_stream, rollout, rollout_split, rollout_stream")
+    if not set(sides) <= set(ALL_SIDES):
+        raise SystemExit("--sides: " + ", ".join(ALL_SIDES))
+    label = a.actions == "label"
+    if label and not set(sides) <= {"stream"} | set(KTICK_TEACH):
+        raise SystemExit("--actions label: sides stream, rollout_teach, rollout_teach_stream only")
     n = a.envs
     lines = []
     worlds = {"w3": ("craft_medium_12x12", 12), "w5": ("craft_medium_12x12_w5", 12)}
@@ -153,7 +219,11 @@ def main():
         bufs = {"obs": next(iter(sims.values())).empty_obs(), "done": torch.empty(n, dtype=torch.uint8, device="cuda"),
                 "end": torch.empty(n, **i32), "pose": torch.empty(n, **i32), "now": torch.empty(n, **i32),
                 "actions": (torch.arange(n, **i32) % 5) if a.actions == "nostop" else None}
-        if set(sides) & set(KTICK):
+        if set(sides) & set(KTICK_TEACH) or label:
+            bufs["label_ring"] = torch.empty((a.ring, n), **i32)
+            bufs["label_in"] = torch.empty(n, **i32)
+            bufs["ones"] = torch.ones(n, dtype=torch.uint8, device="cuda")
+        if set(sides) & set(KTICK + KTICK_TEACH):
             bufs["ring"] = torch.empty((a.ring, n, bufs["obs"].shape[1]), dtype=bufs["obs"].dtype, device="cuda")
             bufs["ktick_actions"] = (bufs["actions"].repeat(a.ticks, 1).contiguous()
                                      if a.actions == "nostop" else None)
@@ -161,13 +231,18 @@ def main():
                 bufs["one_tick_ring"] = bufs["ring"]
         for teach in (False, True):
             bufs["labels"] = torch.empty(n, **i32) if teach else None
-            run_sides = [k for k in sims if not (teach and k in KTICK)]
+            run_sides = [k for k in sims if not (teach and k in KTICK) and not (not teach and (k in KTICK_TEACH or label))]
             if not run_sides:
                 continue
             us = {k: [] for k in run_sides}
             for r in range(a.runs + 1):          # run 0 warms every side and is dropped
                 for k in run_sides:
-                    if k in KTICK:
+                    if k in KTICK_TEACH:
+                        v = timed_teach_launches(sims[k], k, bufs, r * (a.launches + 1) * a.ticks, a.ticks,
+                                                 a.launches, label)
+                    elif label:
+                        v = timed_label_stream(sims[k], a.steps, bufs, 1 + r * (a.steps + 1))
+                    elif k in KTICK:
                         v = timed_launches(sims[k], k, bufs, r * (a.launches + 1) * a.ticks, a.ticks, a.launches)
                     else:
                         v = timed(sims[k], a.steps, k, bufs, r * (a.steps + 1), specs)
@@ -188,7 +263,8 @@ def main():
             elif len(us) > 1:
                 for hi, lo in (("stream", "step"), ("lang_stream", "lang"), ("lang_stream", "stream"),
                                ("rollout_stream", "rollout"), ("rollout_stream", "rollout_split"),
-                               ("rollout_stream", "stream")):
+                               ("rollout_stream", "stream"), ("rollout_teach_stream", "rollout_teach"),
+                               ("rollout_teach_stream", "stream")):
                     if hi in med and lo in med:
                         line[f"{hi}_minus_{lo}_us"] = round(med[hi] - med[lo], 3)
             print(json.dumps(line), flush=True)
