@@ -147,6 +147,18 @@ craft_host::Facts facts(const craft_sim* s) {
           (int64_t)s->queue.size(), s->q_begun};
 }
 
+// Row r of an [rows][n] array of a K-tick launch (a ring output's slot, a tick's given actions);
+// null stays null.
+template <class T>
+T* ring_row(T* x, int64_t r, int64_t n) {
+  return x ? x + r * n : nullptr;
+}
+
+// Slot r of an [ring][n_envs][F] observation ring in the handle's format, or null.
+void* obs_slot(const craft_sim* s, void* obs, int64_t r) {
+  return ring_row(static_cast<uint8_t*>(obs), r, s->n_envs * s->F * craft_host::obs_elem_size(s->k.obs_fmt));
+}
+
 void latch(craft_sim* s, int code, int64_t slot) {
   int32_t z = 0;
   if (s->err_code.compare_exchange_strong(z, code)) s->err_slot.store(slot);
@@ -1257,19 +1269,18 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
                   void* /*stream*/) {
   if (!s) return CRAFT_EINVAL;
   if (const int rc = craft_host::check_rollout(facts(s), tick0, n_ticks, ring, obs, s->last_error)) return rc;
-  const int esz = craft_host::obs_elem_size(s->k.obs_fmt);
   const int64_t n = s->n_envs;
   for (int32_t k = 0; k < n_ticks; ++k) {
     const int64_t r = (tick0 + k) % ring;            // tick t writes ring slot t % ring
     TickIn in{};
-    in.actions = actions ? actions + (int64_t)k * n : nullptr;
+    in.actions = ring_row(actions, k, n);
     in.seed = action_seed;
     in.tick = tick0 + k;
     in.flags = flags;
-    in.obs = obs ? static_cast<uint8_t*>(obs) + r * n * s->F * esz : nullptr;
-    in.reward = reward ? reward + r * n : nullptr;
-    in.done = done ? done + r * n : nullptr;
-    in.sat = success ? success + r * n : nullptr;
+    in.obs = obs_slot(s, obs, r);
+    in.reward = ring_row(reward, r, n);
+    in.done = ring_row(done, r, n);
+    in.sat = ring_row(success, r, n);
     run_ticks(s, in, nullptr);
   }
   return CRAFT_OK;
@@ -1280,22 +1291,21 @@ int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, 
 int craft_rollout_stream(craft_sim_t* s, const craft_rollout_stream_args_t* x, void* stream) {
   if (!s || !x) return CRAFT_EINVAL;
   if (const int rc = craft_host::check_rollout_stream(facts(s), x, s->last_error)) return rc;
-  const int esz = craft_host::obs_elem_size(s->k.obs_fmt);
   const int64_t n = s->n_envs;
   for (int32_t k = 0; k < x->n_ticks; ++k) {
     const int64_t r = (x->tick0 + k) % x->ring;      // tick t writes ring slot t % ring
     craft_stream_step_args_t t{};
-    t.step.actions = x->actions ? x->actions + (int64_t)k * n : nullptr;
+    t.step.actions = ring_row(x->actions, k, n);
     t.step.action_seed = x->action_seed;
     t.step.tick = x->tick0 + k;
     t.step.flags = x->flags;
-    t.step.obs = x->obs ? static_cast<uint8_t*>(x->obs) + r * n * s->F * esz : nullptr;
-    t.step.reward = x->reward ? x->reward + r * n : nullptr;
-    t.step.done = x->done ? x->done + r * n : nullptr;
-    t.step.success = x->success ? x->success + r * n : nullptr;
-    t.episode_end = x->episode_end ? x->episode_end + r * n : nullptr;
-    t.end_pose = x->end_pose ? x->end_pose + r * n : nullptr;
-    t.episode_now = x->episode_now ? x->episode_now + r * n : nullptr;
+    t.step.obs = obs_slot(s, x->obs, r);
+    t.step.reward = ring_row(x->reward, r, n);
+    t.step.done = ring_row(x->done, r, n);
+    t.step.success = ring_row(x->success, r, n);
+    t.episode_end = ring_row(x->episode_end, r, n);
+    t.end_pose = ring_row(x->end_pose, r, n);
+    t.episode_now = ring_row(x->episode_now, r, n);
     if (const int rc = craft_step_stream(s, &t, stream)) return rc;
   }
   return CRAFT_OK;
@@ -1307,7 +1317,6 @@ int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, voi
   if (!s || !x) return CRAFT_EINVAL;
   if (const int rc = craft_host::check_rollout_teach(facts(s), x, s->last_error)) return rc;
   const bool lsync = x->label_actions != 0 || x->behavior_clone != nullptr;
-  const int esz = craft_host::obs_elem_size(s->k.obs_fmt);
   const int64_t n = s->n_envs;
   std::vector<int32_t> cur(n, 0), lab(n, 0);
   std::vector<uint8_t> src(n, 0);                    // 1: the slot acts on its label
@@ -1318,17 +1327,17 @@ int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, voi
   for (int32_t k = 0; k < x->n_ticks; ++k) {
     const int64_t r = (x->tick0 + k) % x->ring;
     TickIn in{};
-    in.actions = x->actions ? x->actions + (int64_t)k * n : nullptr;
+    in.actions = ring_row(x->actions, k, n);
     in.ref = cur.data();
     in.bc = lsync ? src.data() : nullptr;
     in.seed = x->action_seed;
     in.tick = x->tick0 + k;
     in.flags = x->flags;
-    in.obs = x->obs ? static_cast<uint8_t*>(x->obs) + r * n * s->F * esz : nullptr;
-    in.reward = x->reward ? x->reward + r * n : nullptr;
-    in.done = x->done ? x->done + r * n : nullptr;
-    in.sat = x->success ? x->success + r * n : nullptr;
-    in.rec = x->action_record ? x->action_record + r * n : nullptr;
+    in.obs = obs_slot(s, x->obs, r);
+    in.reward = ring_row(x->reward, r, n);
+    in.done = ring_row(x->done, r, n);
+    in.sat = ring_row(x->success, r, n);
+    in.rec = ring_row(x->action_record, r, n);
     in.label = lab.data();
     run_ticks(s, in, nullptr);
     if (x->labels) std::memcpy(x->labels + r * n, lab.data(), sizeof(int32_t) * n);
@@ -1344,7 +1353,6 @@ int craft_rollout_teach_stream(craft_sim_t* s, const craft_rollout_teach_stream_
   if (const int rc = craft_host::check_rollout_teach_stream(facts(s), x, s->last_error)) return rc;
   const craft_rollout_teach_args_t& p = x->teach;
   const bool lsync = p.label_actions != 0 || p.behavior_clone != nullptr;
-  const int esz = craft_host::obs_elem_size(s->k.obs_fmt);
   const int64_t n = s->n_envs;
   std::vector<int32_t> cur(n, 0), lab(n, 0);
   std::vector<uint8_t> ones;
@@ -1353,21 +1361,21 @@ int craft_rollout_teach_stream(craft_sim_t* s, const craft_rollout_teach_stream_
   for (int32_t k = 0; k < p.n_ticks; ++k) {
     const int64_t r = (p.tick0 + k) % p.ring;        // tick t writes ring slot t % ring
     craft_stream_step_args_t t{};
-    t.step.actions = p.actions ? p.actions + (int64_t)k * n : nullptr;
+    t.step.actions = ring_row(p.actions, k, n);
     t.step.ref_actions = lsync ? cur.data() : nullptr;
     t.step.behavior_clone = p.label_actions ? ones.data() : p.behavior_clone;
     t.step.action_seed = p.action_seed;
     t.step.tick = p.tick0 + k;
     t.step.flags = p.flags;
-    t.step.obs = p.obs ? static_cast<uint8_t*>(p.obs) + r * n * s->F * esz : nullptr;
-    t.step.reward = p.reward ? p.reward + r * n : nullptr;
-    t.step.done = p.done ? p.done + r * n : nullptr;
-    t.step.success = p.success ? p.success + r * n : nullptr;
-    t.step.action_record = p.action_record ? p.action_record + r * n : nullptr;
+    t.step.obs = obs_slot(s, p.obs, r);
+    t.step.reward = ring_row(p.reward, r, n);
+    t.step.done = ring_row(p.done, r, n);
+    t.step.success = ring_row(p.success, r, n);
+    t.step.action_record = ring_row(p.action_record, r, n);
     t.label_out = lab.data();
-    t.episode_end = x->episode_end ? x->episode_end + r * n : nullptr;
-    t.end_pose = x->end_pose ? x->end_pose + r * n : nullptr;
-    t.episode_now = x->episode_now ? x->episode_now + r * n : nullptr;
+    t.episode_end = ring_row(x->episode_end, r, n);
+    t.end_pose = ring_row(x->end_pose, r, n);
+    t.episode_now = ring_row(x->episode_now, r, n);
     if (const int rc = craft_step_stream(s, &t, stream)) return rc;
     if (p.labels) std::memcpy(p.labels + r * n, lab.data(), sizeof(int32_t) * n);
     cur.swap(lab);

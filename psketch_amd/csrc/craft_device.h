@@ -173,6 +173,26 @@ inline int resident_workgroups(int threads, size_t lds) {
   return r;
 }
 
+// A persistent launch of KERNEL(v, a) over `units` work units: the workgroups the device holds at
+// once (occupancy of this kernel at this LDS size, raised past 64 KiB first), spread so that every
+// workgroup runs the same number of units (no partial last round), at most one per stats_part row
+// (every workgroup owns one; the handle has (n_envs + 15) / 16 of them).  Reports its grid in
+// a.grid_out; no units, no launch.
+template <auto KERNEL, class ARGS>
+inline hipError_t launch_persistent(int threads, size_t lds, int64_t units, const SimView& v, const ARGS& a,
+                                    hipStream_t st) {
+  if (units == 0) return hipSuccess;
+  const hipError_t e = ensure_lds<KERNEL>(lds);
+  if (e != hipSuccess) return e;
+  const int resident = resident_workgroups<KERNEL>(threads, lds);
+  const int64_t rounds = (units + resident - 1) / resident;
+  const int64_t rows = (v.n_envs + kMinTileEnvs - 1) / kMinTileEnvs;
+  const int64_t grid = std::min<int64_t>((units + rounds - 1) / rounds, rows);
+  if (a.grid_out) *a.grid_out = grid;
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3(threads), lds, st, v, a);
+  return hipGetLastError();
+}
+
 // envs per tile of the teacher-labelled K-tick rollout (craft_rollout_teach.h rt_tile): 32 for
 // 3x3 windows, 16 for wider ones
 __host__ __device__ constexpr int rt_tile_of(int win) { return win == 3 ? 32 : 16; }

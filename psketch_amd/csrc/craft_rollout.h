@@ -337,23 +337,10 @@ __global__ __launch_bounds__(NT, WPE) void rollout_kernel(SimView v, RolloutArgs
 template <int WIN, int TILE, int NT, int FMT, bool GIVEN>
 static hipError_t launch_rollout_one(const SimView& v, const RolloutArgs& a, size_t lds, hipStream_t st) {
   const int64_t tiles = (v.n_envs + TILE - 1) / TILE;
-  if (tiles == 0 || a.n_ticks == 0) return hipSuccess;
+  if (a.n_ticks == 0) return hipSuccess;
   constexpr int WPE = WIN == 3 ? 4 : 2;
-  {                        // double-buffered rows past 64 KiB
-    const hipError_t e = ensure_lds<&rollout_kernel<WIN, TILE, NT, FMT, WPE, GIVEN>>(lds);
-    if (e != hipSuccess) return e;
-  }
-  // persistent workgroups: what the chip holds at once (occupancy of this kernel at this LDS
-  // size), spread so that every workgroup runs the same number of units (no partial last round)
-  const int resident = resident_workgroups<&rollout_kernel<WIN, TILE, NT, FMT, WPE, GIVEN>>(NT, lds);
   const int64_t units = tiles * (int64_t)((a.n_ticks + a.chunk - 1) / a.chunk);
-  const int64_t rounds = (units + resident - 1) / resident;
-  // every workgroup owns one stats_part row; the handle has (n_envs + 15) / 16 of them
-  const int64_t rows = (v.n_envs + kMinTileEnvs - 1) / kMinTileEnvs;
-  const int64_t grid = std::min<int64_t>((units + rounds - 1) / rounds, rows);
-  if (a.grid_out) *a.grid_out = grid;
-  hipLaunchKernelGGL((rollout_kernel<WIN, TILE, NT, FMT, WPE, GIVEN>), dim3((unsigned)grid), dim3(NT), lds, st, v, a);
-  return hipGetLastError();
+  return launch_persistent<&rollout_kernel<WIN, TILE, NT, FMT, WPE, GIVEN>>(NT, lds, units, v, a, st);
 }
 
 // The split-producer kernel (craft_rollout_split.h) for 16- and 32-env tiles: NT threads =
@@ -363,29 +350,15 @@ static hipError_t launch_rollout_one(const SimView& v, const RolloutArgs& a, siz
 template <int WIN, int TILE, int NT, int FMT, bool GIVEN>
 static hipError_t launch_rollout_split_one(const SimView& v, const RolloutArgs& a, hipStream_t st) {
   const int64_t tiles = (v.n_envs + TILE - 1) / TILE;
-  if (tiles == 0 || a.n_ticks == 0) return hipSuccess;
+  if (a.n_ticks == 0) return hipSuccess;
   constexpr int WPE = WIN == 3 ? CRAFT_SPLIT_WPE : 2;
   // the continuous-pipeline instantiation exists for the default 3x3 shape only
   constexpr bool kFlatShape = WIN == 3 && TILE == 32 && NT == 512;
   const bool flat = kFlatShape && a.flat;
   const size_t lds = (size_t)split_lds_bytes(TILE, v.GS, v.F, v.CS, flat);
-  auto kern = flat ? rollout_split_kernel<WIN, TILE, NT, FMT, WPE, GIVEN, kFlatShape>
-                   : rollout_split_kernel<WIN, TILE, NT, FMT, WPE, GIVEN, false>;
-  {
-    const hipError_t e = flat ? ensure_lds<&rollout_split_kernel<WIN, TILE, NT, FMT, WPE, GIVEN, kFlatShape>>(lds)
-                              : ensure_lds<&rollout_split_kernel<WIN, TILE, NT, FMT, WPE, GIVEN, false>>(lds);
-    if (e != hipSuccess) return e;
-  }
-  // persistent workgroups: what the device holds at once (cached per device and LDS size)
-  const int resident = flat ? resident_workgroups<&rollout_split_kernel<WIN, TILE, NT, FMT, WPE, GIVEN, kFlatShape>>(NT, lds)
-                            : resident_workgroups<&rollout_split_kernel<WIN, TILE, NT, FMT, WPE, GIVEN, false>>(NT, lds);
   const int64_t units = tiles * (int64_t)((a.n_ticks + a.chunk - 1) / a.chunk);
-  const int64_t rounds = (units + resident - 1) / resident;
-  const int64_t rows = (v.n_envs + kMinTileEnvs - 1) / kMinTileEnvs;
-  const int64_t grid = std::min<int64_t>((units + rounds - 1) / rounds, rows);
-  if (a.grid_out) *a.grid_out = grid;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, st, v, a);
-  return hipGetLastError();
+  if (flat) return launch_persistent<&rollout_split_kernel<WIN, TILE, NT, FMT, WPE, GIVEN, kFlatShape>>(NT, lds, units, v, a, st);
+  return launch_persistent<&rollout_split_kernel<WIN, TILE, NT, FMT, WPE, GIVEN, false>>(NT, lds, units, v, a, st);
 }
 
 // The handle's observation format and whether the actions are given, as template arguments:

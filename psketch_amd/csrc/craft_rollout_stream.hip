@@ -14,21 +14,9 @@ hipError_t launch_one(const SimView& v, const RolloutArgs& a, hipStream_t st) {
   constexpr int NT = 512;
   constexpr int WPE = WIN == 3 ? CRAFT_SPLIT_WPE : 2;
   const int64_t tiles = (v.n_envs + TILE - 1) / TILE;
-  if (tiles == 0 || a.n_ticks == 0) return hipSuccess;
+  if (a.n_ticks == 0) return hipSuccess;
   const size_t lds = (size_t)split_lds_bytes(TILE, v.GS, v.F, v.CS, false);
-  constexpr auto kern = &rollout_split_kernel<WIN, TILE, NT, FMT, WPE, GIVEN, false, true>;
-  {
-    const hipError_t e = ensure_lds<kern>(lds);
-    if (e != hipSuccess) return e;
-  }
-  // persistent workgroups, every one the same number of units (craft_rollout.h)
-  const int resident = resident_workgroups<kern>(NT, lds);
-  const int64_t rounds = (tiles + resident - 1) / resident;
-  const int64_t rows = (v.n_envs + kMinTileEnvs - 1) / kMinTileEnvs;   // one stats_part row per workgroup
-  const int64_t grid = std::min<int64_t>((tiles + rounds - 1) / rounds, rows);
-  if (a.grid_out) *a.grid_out = grid;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, st, v, a);
-  return hipGetLastError();
+  return launch_persistent<&rollout_split_kernel<WIN, TILE, NT, FMT, WPE, GIVEN, false, true>>(NT, lds, tiles, v, a, st);
 }
 
 template <int WIN>

@@ -1301,4 +1301,42 @@ __global__ __launch_bounds__(kRtThreads, 4) void rollout_teach_kernel(SimView v,
   if (tid == 0) add_stats(v, (int64_t)blockIdx.x, n_succ, n_end, n_step);
 }
 
+// The launch ladder, templated on QUEUE: one instantiation per window, BFS word count and label
+// source, on rt_tile(window) envs, one work unit per tile for the whole launch.  Each .hip file
+// instantiates its own QUEUE, so the kernels stay spread over two translation units.
+// `lds_extra`: bytes past the carve (a diagnostic build's stamp sums).
+template <bool QUEUE, int WIN, int NW, bool LA>
+static hipError_t launch_rt_one(const SimView& v, const RolloutArgs& a, size_t lds_extra, hipStream_t st) {
+  constexpr int TILE = rt_tile(WIN);
+  const int64_t tiles = (v.n_envs + TILE - 1) / TILE;
+  if (a.n_ticks == 0) return hipSuccess;
+  const size_t lds = (size_t)rt_lds(TILE, v.GS, v.F, NW, QUEUE).bytes + lds_extra;
+  return launch_persistent<&rollout_teach_kernel<WIN, TILE, NW, LA, QUEUE>>(kRtThreads, lds, tiles, v, a, st);
+}
+
+template <bool QUEUE, int WIN, bool LA>
+static hipError_t launch_rt_nw(int nw, const SimView& v, const RolloutArgs& a, size_t lds_extra, hipStream_t st) {
+  // nw = 32-bit words per BFS cell set (the band of columns 1 .. W-2): 8x8 -> 2, 10x10 -> 3 (run
+  // as 4), 12x12 -> 4, up to 15x15 -> 7 (run as 8)
+  if (nw <= 2) return launch_rt_one<QUEUE, WIN, 2, LA>(v, a, lds_extra, st);
+  if (nw <= 4) return launch_rt_one<QUEUE, WIN, 4, LA>(v, a, lds_extra, st);
+  return launch_rt_one<QUEUE, WIN, 8, LA>(v, a, lds_extra, st);
+}
+
+template <bool QUEUE, int WIN>
+static hipError_t launch_rt_win(int nw, const SimView& v, const RolloutArgs& a, size_t lds_extra, hipStream_t st) {
+  // labels feeding actions, the transition wave looking them up (lsync 2): the LA kernel
+  if (a.lsync == 2) return launch_rt_nw<QUEUE, WIN, true>(nw, v, a, lds_extra, st);
+  return launch_rt_nw<QUEUE, WIN, false>(nw, v, a, lds_extra, st);
+}
+
+template <bool QUEUE>
+static hipError_t launch_rt(int win, int nw, const SimView& v, const RolloutArgs& a, size_t lds_extra, hipStream_t st) {
+  switch (win) {
+    case 3: return launch_rt_win<QUEUE, 3>(nw, v, a, lds_extra, st);
+    case 5: return launch_rt_win<QUEUE, 5>(nw, v, a, lds_extra, st);
+    default: return launch_rt_win<QUEUE, 7>(nw, v, a, lds_extra, st);
+  }
+}
+
 }  // namespace craft

@@ -441,6 +441,117 @@ void ensure_table(craft_sim* s, int max_clearable) {
   s->view.tt_nsub = 1 << m;
 }
 
+// The tile kernel's arguments of a (checked) craft_step_args_t.
+TileArgs step_args(const craft_sim_t* s, const craft_step_args_t* x) {
+  TileArgs a{};
+  a.actions = x->actions;
+  a.seed = x->action_seed;
+  a.tick = x->tick;
+  a.flags = x->flags;
+  a.n = s->n_envs;
+  a.obs = x->obs;
+  a.reward = x->reward;
+  a.done = x->done;
+  a.sat = x->success;
+  a.ref = x->ref_actions;
+  a.bc = x->behavior_clone;
+  a.rec = x->action_record;
+  a.any_live = x->any_live;
+  a.code = x->transition_code;
+  return a;
+}
+
+// The same of a (checked) craft_lang_step_args_t.
+TileArgs lang_args(const craft_sim_t* s, const craft_lang_step_args_t& x) {
+  TileArgs a{};
+  a.actions = x.actions;
+  a.ref = x.alt_actions;
+  a.bc = x.use_alt;
+  a.seed = x.action_seed;
+  a.tick = x.tick;
+  a.n = s->n_envs;
+  a.obs = x.obs;
+  a.done = x.done;
+  a.sat = x.success;
+  a.rec = x.action_record;
+  a.ask = x.ask_record;
+  a.code = x.transition_code;
+  a.any_live = x.any_live;
+  a.label = x.label_out;
+  return a;
+}
+
+// Puts the handle's episode queue and a stream entry's three extra outputs on the argument block
+// of its kernel (TileArgs or RolloutArgs: the same member names).
+template <class ARGS, class X>
+void queue_args(const craft_sim_t* s, const X& x, ARGS& a) {
+  a.q_entries = s->d_queue;
+  a.q_cursor = s->d_cursor;
+  a.q_count = (uint32_t)s->q_count;
+  a.q_step = s->q_step;
+  a.q_wrap = s->q_wrap;
+  a.ep_end = x.episode_end;
+  a.end_pose = x.end_pose;
+  a.ep_now = x.episode_now;
+}
+
+// The fields every K-tick launch shares, of a (checked) craft_rollout_stream_args_t or
+// craft_rollout_teach_args_t (the same member names).
+template <class X>
+craft::RolloutArgs rollout_args(const X& x) {
+  craft::RolloutArgs a{};
+  a.actions = x.actions;
+  a.seed = x.action_seed;
+  a.tick0 = x.tick0;
+  a.n_ticks = x.n_ticks;
+  a.ring = x.ring;
+  a.flags = x.flags;
+  a.obs = x.obs;
+  a.reward = x.reward;
+  a.done = x.done;
+  a.sat = x.success;
+  return a;
+}
+
+// What the two teacher rollouts add to rollout_args, and the view they launch with.
+SimView teach_rollout_args(const craft_sim_t* s, const craft_rollout_teach_args_t& x, craft::RolloutArgs& a) {
+  const bool lsync = x.label_actions != 0 || x.behavior_clone != nullptr;
+  a.label_in = x.label_in;
+  a.bc = x.behavior_clone;
+  a.label_actions = x.label_actions != 0;
+  // 2: the transition wave looks labels up itself and waits only for BFS answers; 1: it waits
+  // for each item's whole row (a task without a hint table: the walk stays with the teacher)
+  a.lsync = lsync ? (s->hint_walk ? 1 : 2) : 0;
+  a.use_table = s->k.teach_table != 2;              // auto = always: the reads overlap the stream
+  a.labels = x.labels;
+  a.rec = x.action_record;
+  SimView v = teach_view(s);
+  // nontemporal observation stores unless tuned: they keep the table's gathered lines in L2
+  // (65,536 envs, 20 ticks: 417 -> 388 us with hashed actions, 539 -> 467 us with label actions)
+  v.obs_policy = s->obs_store_tuned ? s->rollout_obs_policy : 1;
+  return v;
+}
+
+// A K-tick launch of one work unit per tile of `tile` envs, all a.n_ticks ticks each
+// (craft_rollout_stream, craft_rollout_teach, craft_rollout_teach_stream): the sync area, the
+// launch itself (`go(st)`, reading `a`), then the work-unit counter as craft_rollout's split kernel uses it
+// (queue[1], one claim past the last unit per workgroup).
+template <class GO>
+int launch_tile_units(craft_sim_t* s, int tile, craft::RolloutArgs& a, void* stream, const char* what, GO go) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  a.chunk = a.n_ticks;
+  bool captured = false;
+  const int rc = rollout_sync(s, st, false, a, captured);
+  if (rc != CRAFT_OK) return rc;
+  int64_t grid = 0;
+  a.grid_out = &grid;
+  const int64_t units = (s->n_envs + tile - 1) / tile;
+  const hipError_t e = go(st);
+  if (e != hipSuccess) return hip_fail(s, e, what);
+  if (!captured && grid > 0) s->queue1_next += (uint64_t)std::max<int64_t>(units, grid);
+  return CRAFT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -867,28 +978,6 @@ int craft_step(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, int
   return craft_step_ex(s, &x, stream);
 }
 
-namespace {
-// The tile kernel's arguments of a (checked) craft_step_args_t.
-TileArgs step_args(const craft_sim_t* s, const craft_step_args_t* x) {
-  TileArgs a{};
-  a.actions = x->actions;
-  a.seed = x->action_seed;
-  a.tick = x->tick;
-  a.flags = x->flags;
-  a.n = s->n_envs;
-  a.obs = x->obs;
-  a.reward = x->reward;
-  a.done = x->done;
-  a.sat = x->success;
-  a.ref = x->ref_actions;
-  a.bc = x->behavior_clone;
-  a.rec = x->action_record;
-  a.any_live = x->any_live;
-  a.code = x->transition_code;
-  return a;
-}
-}  // namespace
-
 int craft_step_teach(craft_sim_t* s, const craft_step_args_t* x, int32_t* label_out, void* stream) {
   if (!s || !x || !label_out) return CRAFT_EINVAL;
   int rc = craft_host::check_step_teach(facts(s), x, s->last_error);
@@ -912,21 +1001,7 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* strea
   if (!s || !x) return CRAFT_EINVAL;
   int rc = craft_host::check_step_lang(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
-  TileArgs a{};
-  a.actions = x->actions;
-  a.ref = x->alt_actions;
-  a.bc = x->use_alt;
-  a.seed = x->action_seed;
-  a.tick = x->tick;
-  a.n = s->n_envs;
-  a.obs = x->obs;
-  a.done = x->done;
-  a.sat = x->success;
-  a.rec = x->action_record;
-  a.ask = x->ask_record;
-  a.code = x->transition_code;
-  a.any_live = x->any_live;
-  a.label = x->label_out;
+  const TileArgs a = lang_args(s, *x);
   TickPlan p;
   rc = tick_plan(s, x->label_out != nullptr, stream, "craft_step_lang", p);
   if (rc != CRAFT_OK) return rc;
@@ -1009,14 +1084,7 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* s
   if (rc != CRAFT_OK) return rc;
   TileArgs a = step_args(s, &x->step);
   a.label = x->label_out;
-  a.q_entries = s->d_queue;
-  a.q_cursor = s->d_cursor;
-  a.q_count = (uint32_t)s->q_count;
-  a.q_step = s->q_step;
-  a.q_wrap = s->q_wrap;
-  a.ep_end = x->episode_end;
-  a.end_pose = x->end_pose;
-  a.ep_now = x->episode_now;
+  queue_args(s, *x, a);
   TickPlan p;
   rc = tick_plan(s, x->label_out != nullptr, stream, "craft_step_stream", p);
   if (rc != CRAFT_OK) return rc;
@@ -1030,32 +1098,10 @@ int craft_step_lang_stream(craft_sim_t* s, const craft_lang_stream_step_args_t* 
   if (!s || !x) return CRAFT_EINVAL;
   int rc = craft_host::check_step_lang_stream(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
-  const craft_lang_step_args_t& l = x->step;
-  TileArgs a{};
-  a.actions = l.actions;
-  a.ref = l.alt_actions;
-  a.bc = l.use_alt;
-  a.seed = l.action_seed;
-  a.tick = l.tick;
-  a.n = s->n_envs;
-  a.obs = l.obs;
-  a.done = l.done;
-  a.sat = l.success;
-  a.rec = l.action_record;
-  a.ask = l.ask_record;
-  a.code = l.transition_code;
-  a.any_live = l.any_live;
-  a.label = l.label_out;
-  a.q_entries = s->d_queue;
-  a.q_cursor = s->d_cursor;
-  a.q_count = (uint32_t)s->q_count;
-  a.q_step = s->q_step;
-  a.q_wrap = s->q_wrap;
-  a.ep_end = x->episode_end;
-  a.end_pose = x->end_pose;
-  a.ep_now = x->episode_now;
+  TileArgs a = lang_args(s, x->step);
+  queue_args(s, *x, a);
   TickPlan p;
-  rc = tick_plan(s, l.label_out != nullptr, stream, "craft_step_lang_stream", p);
+  rc = tick_plan(s, x->step.label_out != nullptr, stream, "craft_step_lang_stream", p);
   if (rc != CRAFT_OK) return rc;
   const hipError_t e = craft::launch_tick_lang_stream(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
                                                       reinterpret_cast<hipStream_t>(stream));
@@ -1119,44 +1165,16 @@ int craft_rollout_stream(craft_sim_t* s, const craft_rollout_stream_args_t* x, v
   int rc = craft_host::check_rollout_stream(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
   if (x->n_ticks == 0) return CRAFT_OK;
-  craft::RolloutArgs a{};
-  a.actions = x->actions;
-  a.seed = x->action_seed;
-  a.tick0 = x->tick0;
-  a.n_ticks = x->n_ticks;
-  a.ring = x->ring;
-  a.flags = x->flags;
-  a.obs = x->obs;
-  a.reward = x->reward;
-  a.done = x->done;
-  a.sat = x->success;
-  a.chunk = x->n_ticks;                           // one unit per tile: all n_ticks ticks
-  a.q_entries = s->d_queue;
-  a.q_cursor = s->d_cursor;
-  a.q_count = (uint32_t)s->q_count;
-  a.q_step = s->q_step;
-  a.q_wrap = s->q_wrap;
-  a.ep_end = x->episode_end;
-  a.end_pose = x->end_pose;
-  a.ep_now = x->episode_now;
+  craft::RolloutArgs a = rollout_args(*x);
+  queue_args(s, *x, a);
   // 32-env tiles; 16 where craft_sim_tune says so or where 32 envs' two staged observation
   // buffers exceed a workgroup's 160 KiB of LDS (the largest tile that fits)
   const int tile = craft::rollout_stream_tile(s->k.tile_knob, s->view);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // the work-unit counter as craft_rollout's split kernel uses it (queue[1], one claim past the
-  // last unit per workgroup)
-  bool captured = false;
-  rc = rollout_sync(s, st, false, a, captured);
-  if (rc != CRAFT_OK) return rc;
-  int64_t grid = 0;
-  a.grid_out = &grid;
   SimView view = s->view;
   view.obs_policy = s->rollout_obs_policy;
-  const int64_t units = (s->n_envs + tile - 1) / tile;
-  const hipError_t e = craft::launch_rollout_stream(s->cfg.window_width, tile, view, a, st);
-  if (e != hipSuccess) return hip_fail(s, e, "craft_rollout_stream launch");
-  if (!captured && grid > 0) s->queue1_next += (uint64_t)std::max<int64_t>(units, grid);
-  return CRAFT_OK;
+  return launch_tile_units(s, tile, a, stream, "craft_rollout_stream launch", [&](hipStream_t st) {
+    return craft::launch_rollout_stream(s->cfg.window_width, tile, view, a, st);
+  });
 }
 
 int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, void* stream) {
@@ -1164,101 +1182,32 @@ int craft_rollout_teach(craft_sim_t* s, const craft_rollout_teach_args_t* x, voi
   int rc = craft_host::check_rollout_teach(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
   if (x->n_ticks == 0) return CRAFT_OK;
-  const bool lsync = x->label_actions != 0 || x->behavior_clone != nullptr;
-  craft::RolloutArgs a{};
-  a.actions = x->actions;
-  a.seed = x->action_seed;
-  a.tick0 = x->tick0;
-  a.n_ticks = x->n_ticks;
-  a.ring = x->ring;
-  a.flags = x->flags;
-  a.obs = x->obs;
-  a.reward = x->reward;
-  a.done = x->done;
-  a.sat = x->success;
-  a.chunk = x->n_ticks;                           // one unit per tile: all n_ticks ticks
-  a.label_in = x->label_in;
-  a.bc = x->behavior_clone;
-  a.label_actions = x->label_actions != 0;
-  // 2: the transition wave looks labels up itself and waits only for BFS answers; 1: it waits
-  // for each item's whole row (a task without a hint table: the walk stays with the teacher)
-  a.lsync = lsync ? (s->hint_walk ? 1 : 2) : 0;
-  a.use_table = s->k.teach_table != 2;              // auto = always: the reads overlap the stream
-  a.labels = x->labels;
-  a.rec = x->action_record;
+  craft::RolloutArgs a = rollout_args(*x);
+  const SimView v = teach_rollout_args(s, *x, a);
   rc = flush_table(s, stream, "craft_rollout_teach");
   if (rc != CRAFT_OK) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // the work-unit counter as craft_rollout's split kernel uses it (queue[1], one claim past the
-  // last unit per workgroup)
-  bool captured = false;
-  rc = rollout_sync(s, st, false, a, captured);
-  if (rc != CRAFT_OK) return rc;
-  int64_t grid = 0;
-  a.grid_out = &grid;
-  SimView v = teach_view(s);
-  // nontemporal observation stores unless tuned: they keep the table's gathered lines in L2
-  // (65,536 envs, 20 ticks: 417 -> 388 us with hashed actions, 539 -> 467 us with label actions)
-  v.obs_policy = s->obs_store_tuned ? s->rollout_obs_policy : 1;
-  const int64_t units = (s->n_envs + craft::rt_tile_of(s->cfg.window_width) - 1) / craft::rt_tile_of(s->cfg.window_width);
-  hipError_t e = craft::launch_rollout_teach(s->cfg.window_width, craft::teach_words(s->view.W, s->view.H), v, a, st);
-  if (e != hipSuccess) return hip_fail(s, e, "craft_rollout_teach launch");
-  if (!captured && grid > 0) s->queue1_next += (uint64_t)std::max<int64_t>(units, grid);
-  return CRAFT_OK;
+  return launch_tile_units(s, craft::rt_tile_of(s->cfg.window_width), a, stream, "craft_rollout_teach launch",
+                           [&](hipStream_t st) {
+                             return craft::launch_rollout_teach(s->cfg.window_width,
+                                                                craft::teach_words(s->view.W, s->view.H), v, a, st);
+                           });
 }
 
 int craft_rollout_teach_stream(craft_sim_t* s, const craft_rollout_teach_stream_args_t* x, void* stream) {
   if (!s || !x) return CRAFT_EINVAL;
   int rc = craft_host::check_rollout_teach_stream(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
-  const craft_rollout_teach_args_t& t = x->teach;
-  if (t.n_ticks == 0) return CRAFT_OK;
-  const bool lsync = t.label_actions != 0 || t.behavior_clone != nullptr;
-  craft::RolloutArgs a{};
-  a.actions = t.actions;
-  a.seed = t.action_seed;
-  a.tick0 = t.tick0;
-  a.n_ticks = t.n_ticks;
-  a.ring = t.ring;
-  a.flags = t.flags;
-  a.obs = t.obs;
-  a.reward = t.reward;
-  a.done = t.done;
-  a.sat = t.success;
-  a.chunk = t.n_ticks;                            // one unit per tile: all n_ticks ticks
-  a.label_in = t.label_in;
-  a.bc = t.behavior_clone;
-  a.label_actions = t.label_actions != 0;
-  a.lsync = lsync ? (s->hint_walk ? 1 : 2) : 0;     // as craft_rollout_teach
-  a.use_table = s->k.teach_table != 2;
-  a.labels = t.labels;
-  a.rec = t.action_record;
-  a.q_entries = s->d_queue;
-  a.q_cursor = s->d_cursor;
-  a.q_count = (uint32_t)s->q_count;
-  a.q_step = s->q_step;
-  a.q_wrap = s->q_wrap;
-  a.ep_end = x->episode_end;
-  a.end_pose = x->end_pose;
-  a.ep_now = x->episode_now;
+  if (x->teach.n_ticks == 0) return CRAFT_OK;
+  craft::RolloutArgs a = rollout_args(x->teach);
+  const SimView v = teach_rollout_args(s, x->teach, a);
+  queue_args(s, *x, a);
   rc = flush_table(s, stream, "craft_rollout_teach_stream");
   if (rc != CRAFT_OK) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // the work-unit counter as craft_rollout_teach uses it (queue[1], one claim past the last unit
-  // per workgroup)
-  bool captured = false;
-  rc = rollout_sync(s, st, false, a, captured);
-  if (rc != CRAFT_OK) return rc;
-  int64_t grid = 0;
-  a.grid_out = &grid;
-  SimView v = teach_view(s);
-  v.obs_policy = s->obs_store_tuned ? s->rollout_obs_policy : 1;   // nontemporal unless tuned (craft_rollout_teach)
-  const int tile = craft::rt_tile_of(s->cfg.window_width);
-  const int64_t units = (s->n_envs + tile - 1) / tile;
-  const hipError_t e = craft::launch_rollout_teach_stream(s->cfg.window_width, craft::teach_words(s->view.W, s->view.H), v, a, st);
-  if (e != hipSuccess) return hip_fail(s, e, "craft_rollout_teach_stream launch");
-  if (!captured && grid > 0) s->queue1_next += (uint64_t)std::max<int64_t>(units, grid);
-  return CRAFT_OK;
+  return launch_tile_units(s, craft::rt_tile_of(s->cfg.window_width), a, stream, "craft_rollout_teach_stream launch",
+                           [&](hipStream_t st) {
+                             return craft::launch_rollout_teach_stream(
+                                 s->cfg.window_width, craft::teach_words(s->view.W, s->view.H), v, a, st);
+                           });
 }
 
 int craft_stats(craft_sim_t* s, int64_t* stats_out, int32_t reset, void* stream) {

@@ -271,6 +271,59 @@ class CraftSim:
                                   ("transition_code", transition_code, torch.int8, (n,)),
                                   ("obs", obs, self.obs_dtype, (n, self.n_features))))
 
+    def _lang_fields(self, st, keep, actions, alt_actions, use_alt, obs, done, success, action_record,
+                     ask_record, transition_code, any_live, labels):
+        """The pointer fields of a craft_lang_step_args_t (step_lang, step_lang_stream)."""
+        n = self.n_envs
+        if actions is not None:
+            _put(st, keep, "actions", self._i32(actions, n))
+        if alt_actions is not None:
+            _put(st, keep, "alt_actions", self._i32(alt_actions, n))
+        if use_alt is not None:
+            _put(st, keep, "use_alt", self._flag_mask("use_alt", use_alt, n))
+        self._put_bufs(st, keep, (("done", done, torch.uint8, (n,)),
+                                  ("success", success, torch.int8, (n,)),
+                                  ("action_record", action_record, torch.int32, (n,)),
+                                  ("ask_record", ask_record, torch.int8, (n,)),
+                                  ("transition_code", transition_code, torch.int8, (n,)),
+                                  ("any_live", any_live, torch.int32, (1,)),
+                                  ("label_out", labels, torch.int32, (n,)),
+                                  ("obs", obs, self.obs_dtype, (n, self.n_features))))
+
+    def _queue_outs(self, st, keep, shape, episode_end, end_pose, episode_now):
+        """The three int32 outputs every stream entry adds, of `shape`: (n,) or (ring, n)."""
+        self._put_bufs(st, keep, (("episode_end", episode_end, torch.int32, shape),
+                                  ("end_pose", end_pose, torch.int32, shape),
+                                  ("episode_now", episode_now, torch.int32, shape)))
+
+    def _rollout_fields(self, st, keep, n_ticks, seed, tick0, flags, actions, obs, reward, done, success,
+                        more=(), queue=None):
+        """The ring outputs, the actions and the five launch words of a struct-taking K-tick
+        rollout (rollout_stream, rollout_teach, rollout_teach_stream): obs [R, N, F] and reward,
+        done, success [R, N], then `more` ((field, tensor) rows: the entry's further int32 [R, N]
+        outputs), then the queue outputs (queue: the struct that holds them, episode_end,
+        end_pose, episode_now).  R is that of the first ring given."""
+        n = self.n_envs
+        named = [("obs", obs), ("reward", reward), ("done", done), ("success", success), *more]
+        if queue is not None:
+            named += (("episode_end", queue[1]), ("end_pose", queue[2]), ("episode_now", queue[3]))
+        ring = _ring_extent(named, n) or 1
+        shape = (ring, n)
+        self._put_bufs(st, keep, [("obs", obs, self.obs_dtype, (ring, n, self.n_features)),
+                                  ("reward", reward, torch.float32, shape),
+                                  ("done", done, torch.uint8, shape),
+                                  ("success", success, torch.int8, shape),
+                                  *[(field, t, torch.int32, shape) for field, t in more]])
+        if queue is not None:
+            self._queue_outs(queue[0], keep, shape, *queue[1:])
+        if actions is not None:
+            _put(st, keep, "actions", self._i32(actions, n * n_ticks))
+        st.action_seed = seed & (2**64 - 1)
+        st.tick0 = int(tick0)
+        st.n_ticks = int(n_ticks)
+        st.flags = flags
+        st.ring = int(ring)
+
     def empty_obs(self, n=None):
         n = self.n_envs if n is None else n
         return torch.empty((n, self.n_features), dtype=self.obs_dtype, device=self.device)
@@ -375,21 +428,10 @@ class CraftSim:
         None), action_record int32 and ask_record int8 (-1 for a slot done before the tick),
         transition_code int8, any_live int32 [1], labels int32 [N]: the DemonstrationTeacher on
         every new state in the same launch (-1 for a slot done before the tick)."""
-        n = self.n_envs
         args = N.craft_lang_step_args_t()
         keep = []
-        _put(args, keep, "actions", self._i32(actions, n) if actions is not None else None)
-        _put(args, keep, "alt_actions", self._i32(alt_actions, n) if alt_actions is not None else None)
-        if use_alt is not None:
-            _put(args, keep, "use_alt", self._flag_mask("use_alt", use_alt, n))
-        self._put_bufs(args, keep, (("done", done, torch.uint8, (n,)),
-                                    ("success", success, torch.int8, (n,)),
-                                    ("action_record", action_record, torch.int32, (n,)),
-                                    ("ask_record", ask_record, torch.int8, (n,)),
-                                    ("transition_code", transition_code, torch.int8, (n,)),
-                                    ("any_live", any_live, torch.int32, (1,)),
-                                    ("label_out", labels, torch.int32, (n,)),
-                                    ("obs", obs, self.obs_dtype, (n, self.n_features))))
+        self._lang_fields(args, keep, actions, alt_actions, use_alt, obs, done, success, action_record,
+                          ask_record, transition_code, any_live, labels)
         args.action_seed = seed & (2**64 - 1)
         args.tick = int(tick)
         args.flags = int(flags)
@@ -443,9 +485,8 @@ class CraftSim:
         st.action_seed = seed & (2**64 - 1)
         st.tick = int(tick)
         st.flags = N.STEP_AUTORESET
-        self._put_bufs(args, keep, [(name, t, torch.int32, (n,)) for name, t in (
-            ("label_out", labels), ("episode_end", episode_end), ("end_pose", end_pose),
-            ("episode_now", episode_now))])
+        self._put_bufs(args, keep, (("label_out", labels, torch.int32, (n,)),))
+        self._queue_outs(args, keep, (n,), episode_end, end_pose, episode_now)
         self._check(self._L.craft_step_stream(self._h, ctypes.byref(args), self._stream()),
                     "craft_step_stream")
         return obs
@@ -464,23 +505,12 @@ class CraftSim:
         args = N.craft_lang_stream_step_args_t()
         keep = []
         st = args.step
-        _put(st, keep, "actions", self._i32(actions, n) if actions is not None else None)
-        _put(st, keep, "alt_actions", self._i32(alt_actions, n) if alt_actions is not None else None)
-        if use_alt is not None:
-            _put(st, keep, "use_alt", self._flag_mask("use_alt", use_alt, n))
-        self._put_bufs(st, keep, (("done", done, torch.uint8, (n,)),
-                                  ("success", success, torch.int8, (n,)),
-                                  ("action_record", action_record, torch.int32, (n,)),
-                                  ("ask_record", ask_record, torch.int8, (n,)),
-                                  ("transition_code", transition_code, torch.int8, (n,)),
-                                  ("any_live", any_live, torch.int32, (1,)),
-                                  ("label_out", labels, torch.int32, (n,)),
-                                  ("obs", obs, self.obs_dtype, (n, self.n_features))))
+        self._lang_fields(st, keep, actions, alt_actions, use_alt, obs, done, success, action_record,
+                          ask_record, transition_code, any_live, labels)
         st.action_seed = seed & (2**64 - 1)
         st.tick = int(tick)
         st.flags = int(flags)
-        self._put_bufs(args, keep, [(name, t, torch.int32, (n,)) for name, t in (
-            ("episode_end", episode_end), ("end_pose", end_pose), ("episode_now", episode_now))])
+        self._queue_outs(args, keep, (n,), episode_end, end_pose, episode_now)
         self._check(self._L.craft_step_lang_stream(self._h, ctypes.byref(args), self._stream()),
                     "craft_step_lang_stream")
         return obs
@@ -536,28 +566,12 @@ class CraftSim:
         [n_ticks, N] or None (hashed); obs: [R, N, F] ring in the obs format (tick t writes
         obs[t % R]); reward / done / success / episode_end / end_pose / episode_now: [R, N]
         rings.  R is that of the first ring given."""
-        n = self.n_envs
         if n_ticks < 0:
             raise ValueError("n_ticks must be >= 0")
         args = N.craft_rollout_stream_args_t()
         keep = []
-        ring = _ring_extent((("obs", obs), ("reward", reward), ("done", done), ("success", success),
-                             ("episode_end", episode_end), ("end_pose", end_pose),
-                             ("episode_now", episode_now)), n) or 1
-        self._put_bufs(args, keep, (("obs", obs, self.obs_dtype, (ring, n, self.n_features)),
-                                    ("reward", reward, torch.float32, (ring, n)),
-                                    ("done", done, torch.uint8, (ring, n)),
-                                    ("success", success, torch.int8, (ring, n)),
-                                    ("episode_end", episode_end, torch.int32, (ring, n)),
-                                    ("end_pose", end_pose, torch.int32, (ring, n)),
-                                    ("episode_now", episode_now, torch.int32, (ring, n))))
-        if actions is not None:
-            _put(args, keep, "actions", self._i32(actions, n * n_ticks))
-        args.action_seed = seed & (2**64 - 1)
-        args.tick0 = int(tick0)
-        args.n_ticks = int(n_ticks)
-        args.flags = N.STEP_AUTORESET
-        args.ring = int(ring)
+        self._rollout_fields(args, keep, n_ticks, seed, tick0, N.STEP_AUTORESET, actions, obs, reward, done,
+                             success, queue=(args, episode_end, end_pose, episode_now))
         self._check(self._L.craft_rollout_stream(self._h, ctypes.byref(args), self._stream()),
                     "craft_rollout_stream")
         return obs
@@ -593,26 +607,14 @@ class CraftSim:
                 return labels
         args = N.craft_rollout_teach_args_t()
         keep = []
-        ring = _ring_extent((("obs", obs), ("reward", reward), ("done", done), ("success", success),
-                             ("labels", labels), ("action_record", action_record)), n) or 1
-        self._put_bufs(args, keep, (("obs", obs, self.obs_dtype, (ring, n, self.n_features)),
-                                    ("reward", reward, torch.float32, (ring, n)),
-                                    ("done", done, torch.uint8, (ring, n)),
-                                    ("success", success, torch.int8, (ring, n)),
-                                    ("labels", labels, torch.int32, (ring, n)),
-                                    ("action_record", action_record, torch.int32, (ring, n))))
-        if actions is not None:
-            _put(args, keep, "actions", self._i32(actions, n * n_ticks))
+        self._rollout_fields(args, keep, n_ticks, seed, tick0, N.STEP_AUTORESET if autoreset else 0, actions,
+                             obs, reward, done, success,
+                             more=(("labels", labels), ("action_record", action_record)))
         if label_in is not None:
             _put(args, keep, "label_in", self._i32(label_in, n))
         if behavior_clone is not None:
             _put(args, keep, "behavior_clone", self._flag_mask("behavior_clone", behavior_clone, n))
         args.label_actions = 1 if label_actions else 0
-        args.action_seed = seed & (2**64 - 1)
-        args.tick0 = int(tick0)
-        args.n_ticks = int(n_ticks)
-        args.flags = N.STEP_AUTORESET if autoreset else 0
-        args.ring = int(ring)
         self._check(self._L.craft_rollout_teach(self._h, ctypes.byref(args), self._stream()),
                     "craft_rollout_teach")
         if actions is None and label_in is None and behavior_clone is None and not label_actions:
@@ -640,31 +642,14 @@ class CraftSim:
         args = N.craft_rollout_teach_stream_args_t()
         t = args.teach
         keep = []
-        ring = _ring_extent((("obs", obs), ("reward", reward), ("done", done), ("success", success),
-                             ("labels", labels), ("action_record", action_record),
-                             ("episode_end", episode_end), ("end_pose", end_pose),
-                             ("episode_now", episode_now)), n) or 1
-        self._put_bufs(t, keep, (("obs", obs, self.obs_dtype, (ring, n, self.n_features)),
-                                 ("reward", reward, torch.float32, (ring, n)),
-                                 ("done", done, torch.uint8, (ring, n)),
-                                 ("success", success, torch.int8, (ring, n)),
-                                 ("labels", labels, torch.int32, (ring, n)),
-                                 ("action_record", action_record, torch.int32, (ring, n))))
-        self._put_bufs(args, keep, (("episode_end", episode_end, torch.int32, (ring, n)),
-                                    ("end_pose", end_pose, torch.int32, (ring, n)),
-                                    ("episode_now", episode_now, torch.int32, (ring, n))))
-        if actions is not None:
-            _put(t, keep, "actions", self._i32(actions, n * n_ticks))
+        self._rollout_fields(t, keep, n_ticks, seed, tick0, N.STEP_AUTORESET, actions, obs, reward, done,
+                             success, more=(("labels", labels), ("action_record", action_record)),
+                             queue=(args, episode_end, end_pose, episode_now))
         if label_in is not None:
             _put(t, keep, "label_in", self._i32(label_in, n))
         if behavior_clone is not None:
             _put(t, keep, "behavior_clone", self._flag_mask("behavior_clone", behavior_clone, n))
         t.label_actions = 1 if label_actions else 0
-        t.action_seed = seed & (2**64 - 1)
-        t.tick0 = int(tick0)
-        t.n_ticks = int(n_ticks)
-        t.flags = N.STEP_AUTORESET
-        t.ring = int(ring)
         self._check(self._L.craft_rollout_teach_stream(self._h, ctypes.byref(args), self._stream()),
                     "craft_rollout_teach_stream")
         return labels
