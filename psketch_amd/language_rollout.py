@@ -22,21 +22,19 @@ import torch
 
 from . import _native as N
 from .language import WORDS
-from .rollout import EvalContext, EvalInfo, RolloutError, _live_flags, _queue_pass  # noqa: F401
+from .rollout import (EvalContext, EvalInfo, RolloutError, _Info, _LiveFlags,  # noqa: F401
+                      _actions, _distances, _queue_pass)
 
 MODES = ("primitive", "interactive", "active")
 PAD = "<PAD>"
 ASK = 1            # students/active_primitive_language.py:17
 
 
-class LanguageRolloutInfo:
+class LanguageRolloutInfo(_Info):
     """The rollout's `info` as tensors: action_seqs int32 [T, n] (-1 where the env did not
     act), n_actions int32 [n], success int8 [n] (1 / 0 / -1 for None), distances int32 [n]
     (-1 where the task is not a get task), is_get bool [n], num_interactions, num_steps,
     ticks (of the last pass)."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
     def as_info(self):
         """The reference's info dict (python lists; success keeps None)."""
@@ -52,12 +50,6 @@ class LanguageRolloutInfo:
             "num_interactions": int(self.num_interactions),
             "num_steps": int(self.num_steps),
         }
-
-
-def _actions(a, n, dev):
-    if not torch.is_tensor(a):
-        a = torch.as_tensor(np.asarray(a), device=dev)
-    return a.to(device=dev, dtype=torch.int32).reshape(n).contiguous()
 
 
 class _Pass:
@@ -76,11 +68,7 @@ class _Pass:
         self.success = torch.full((n,), -1, dtype=torch.int8, device=dev)
         self.new_labels = torch.empty(n, dtype=torch.int32, device=dev) if teach else None
         self.ticks = 0
-        if sim._cpu:
-            self.flags, self.flag_dev, self.events = torch.zeros(T + 1, dtype=torch.int32), 0, None
-        else:
-            self.flags, self.flag_dev, self.events = _live_flags(sim, T)
-        self.live = None if self.flag_dev else torch.zeros(T + 1, dtype=torch.int32, device=dev)
+        self.live = _LiveFlags(sim, T)
         self.args = N.craft_lang_step_args_t()
         self.args.done = self.done.data_ptr()
         self.args.success = self.success.data_ptr()
@@ -99,16 +87,11 @@ class _Pass:
         a.action_record = self.seqs[t].data_ptr()
         a.ask_record = self.asks[t].data_ptr()
         a.transition_code = self.codes[t].data_ptr()
-        a.any_live = self.flag_dev + 4 * t if self.flag_dev else self.live[t].data_ptr()
+        a.any_live = self.live.ptr(t)
         sim._check(sim._L.craft_step_lang(sim._h, a, sim._stream()), "craft_step_lang")
         self.ticks = t + 1
-        if sim._cpu:
-            return int(self.live[t]) != 0
-        if not self.flag_dev:
-            self.flags[t:t + 1].copy_(self.live[t:t + 1], non_blocking=True)
-        self.events[t].record()
-        self.events[t].synchronize()
-        return int(self.flags[t]) != 0
+        self.live.record(t)
+        return self.live.wait(t)
 
 
 def do_language_rollout(sim, spec, student, teacher, is_eval, mode, ref_actions=None):
@@ -288,16 +271,10 @@ def _primitive(sim, spec, task, student, teacher, is_eval, ref_actions):
 def _summary(sim, task, p, num_interactions, num_steps, raised):
     """success / distances of the final states (primitive_language.py:121-133) with one
     read-back: craft_rollout_distances, the flags and the latched-error word."""
-    n, dev, t = sim.n_envs, sim.device, p.ticks
+    dev, t = sim.device, p.ticks
     buf = torch.zeros(4, dtype=torch.int32, device=dev)   # [0:2] the two flags, [2] raised
     err = torch.zeros(4, dtype=torch.int32, device=dev)
-    distances = torch.empty(n, dtype=torch.int32, device=dev)
-    is_get = torch.empty(n, dtype=torch.uint8, device=dev)
-    n_actions = torch.empty(n, dtype=torch.int32, device=dev)
-    sim._check(sim._L.craft_rollout_distances(
-        sim._h, task.data_ptr(), p.success.data_ptr(), p.seqs.data_ptr(), p.seqs.shape[0],
-        distances.data_ptr(), is_get.data_ptr(), n_actions.data_ptr(), buf[0:2].data_ptr(),
-        sim._stream()), "craft_rollout_distances")
+    distances, is_get, n_actions = _distances(sim, task, p.success, p.seqs, buf[0:2])
     buf[2] = raised.to(torch.int32)
     sim.error_word(out=err)
     host = torch.cat([buf, err]).cpu().tolist()
@@ -310,5 +287,5 @@ def _summary(sim, task, p, num_interactions, num_steps, raised):
         raise RolloutError("find_closest_resources found no target: len(None) "
                            "(primitive_language.py:129-131)")
     return LanguageRolloutInfo(action_seqs=p.seqs[:t], n_actions=n_actions, success=p.success,
-                               distances=distances, is_get=is_get.view(torch.bool),
+                               distances=distances, is_get=is_get,
                                num_interactions=num_interactions, num_steps=num_steps, ticks=t)

@@ -29,24 +29,27 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .sim import CraftSim
-
+from .sim import CraftSim, _stack_specs
 
 
 class RolloutError(Exception):
     """Raised where the reference's do_rollout raises (TypeError/AssertionError)."""
 
 
-class RolloutInfo:
+class _Info:
+    """A driver's results: the fields its class documents, as attributes."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class RolloutInfo(_Info):
     """do_rollout's `info` as device tensors.
 
     action_seqs int32 [T, n] (-1 after an env's last action), n_actions int32 [n],
     success int8 [n], distances int32 [n] (-1 where the task is not a get task),
     is_get bool [n], num_interactions / num_steps ints, ticks, and obs
     ([T+1, n, F], every observation the student saw) when kept."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
     def to_reference(self):
         """The reference's info dict (python lists, trainers/imitation.py:93-99)."""
@@ -123,11 +126,7 @@ def do_rollout(sim, spec, act, is_eval, behavior_clone=None, receive=None, keep_
     sim.reset(*spec, obs=obs)
     success = torch.zeros(n, dtype=torch.int8, device=dev)
     seqs = torch.full((T, n), -1, dtype=torch.int32, device=dev)
-    # any-live flags (1: some env still running after tick t), one per tick: page-locked host
-    # memory the kernel stores into directly where HIP maps it (read after the tick's event),
-    # else a device array copied back per tick
-    flags, flag_dev, events = _live_flags(sim, T)
-    live = None if flag_dev else torch.zeros(T + 1, dtype=torch.int32, device=dev)
+    live = _LiveFlags(sim, T)
     # ref_actions of every tick: tick t reads refs[t] and (fused) labels refs[t + 1]; receive()
     # gets the row itself (no copy), which no later tick or rollout overwrites
     refs = None if is_eval else torch.empty((T + 1, n), dtype=torch.int32, device=dev)
@@ -143,9 +142,7 @@ def do_rollout(sim, spec, act, is_eval, behavior_clone=None, receive=None, keep_
     if not is_eval and not fused_teacher:
         if sim._cpu:
             raise ValueError("the CPU variant runs the fused teacher only (fused_teacher=True)")
-        side = getattr(sim, "_teacher_stream", None)
-        if side is None:                         # created once per simulator (costly)
-            side = sim._teacher_stream = torch.cuda.Stream(dev)
+        side = _teacher_stream(sim)
     labels_ready = getattr(sim, "_teacher_event", None)
     if labels_ready is None and not sim._cpu:
         labels_ready = sim._teacher_event = torch.cuda.Event()
@@ -163,21 +160,16 @@ def do_rollout(sim, spec, act, is_eval, behavior_clone=None, receive=None, keep_
         """Tick t on the stream: the student's act, then one step launch (behaviour cloning, the
         action record, the any-live flag and, fused, the next tick's labels), then the flag's
         event (after the flag's copy to the host where it is not mapped)."""
-        actions = act(cur["obs"], t)
-        if not torch.is_tensor(actions):
-            actions = torch.as_tensor(np.asarray(actions), device=dev)
-        actions = actions.to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+        actions = _actions(act(cur["obs"], t), n, dev)
         if side is not None:
             main.wait_event(labels_ready)
         if keep_obs:
             cur["obs"] = obs_hist[t + 1]
-        step(t, actions, cur["obs"], None if is_eval else refs[t], seqs[t],
-             flag_dev + 4 * t if flag_dev else live[t].data_ptr(), refs[t + 1] if fused else None)
+        step(t, actions, cur["obs"], None if is_eval else refs[t], seqs[t], live.ptr(t),
+             refs[t + 1] if fused else None)
         if side is not None and t + 1 < T:
             launch_teacher(t + 1)                # speculative: all -1 if every env is done
-        if not flag_dev:
-            flags[t:t + 1].copy_(live[t:t + 1], non_blocking=True)
-        events[t].record()
+        live.record(t)
 
     if not is_eval:
         if fused_teacher:
@@ -193,11 +185,11 @@ def do_rollout(sim, spec, act, is_eval, behavior_clone=None, receive=None, keep_
     while True:
         if lookahead and t + 1 < T:
             issue(t + 1)
-        events[t].synchronize()
+        more = live.wait(t)
         if not is_eval and receive is not None:
             receive(refs[t])                     # tick t is real
         t += 1
-        if t >= T or int(flags[t - 1]) == 0:
+        if t >= T or not more:
             break
         if not lookahead:
             issue(t)
@@ -264,9 +256,10 @@ def _graph_rollout(sim, spec, act, is_eval, behavior_clone, receive, keep_obs, t
         raise ValueError("max_timesteps must be positive")
     spec = [sim._i32(a, n) for a in spec]
     task = spec[4]
-    flags, flag_dev, events = _live_flags(sim, T)
-    if not flag_dev:
+    live = _LiveFlags(sim, T)
+    if not live.dev:
         raise RuntimeError("graph mode needs the any-live flags in mapped host memory")
+    flags, events = live.host, live.events       # one event per chunk, read flag by flag
     gs = getattr(sim, "_graph_state", None)
     side_teacher = not is_eval and not fused_teacher
     key = (is_eval, G, T, graph_key, side_teacher)
@@ -290,11 +283,7 @@ def _graph_rollout(sim, spec, act, is_eval, behavior_clone, receive, keep_obs, t
     if not gs["graphs"]:
         step = _stepper(sim, not is_eval and not side_teacher, gs["bc"], success)
         main = torch.cuda.current_stream(dev)
-        side = None
-        if side_teacher:                         # created once per simulator (costly)
-            side = getattr(sim, "_teacher_stream", None)
-            if side is None:
-                side = sim._teacher_stream = torch.cuda.Stream(dev)
+        side = _teacher_stream(sim) if side_teacher else None
 
         def issue(t):
             # (side teacher) tick t's ref_actions, the labels of the states tick t - 1 left, on a
@@ -305,11 +294,10 @@ def _graph_rollout(sim, spec, act, is_eval, behavior_clone, receive, keep_obs, t
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
                     sim.teacher(action_out=refs[t])
-            actions = act(obs, t)
-            actions = actions.to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+            actions = _actions(act(obs, t), n, dev)
             if side is not None and t > 0:
                 cur.wait_stream(side)
-            step(t, actions, obs, None if is_eval else refs[t], seqs[t], flag_dev + 4 * t,
+            step(t, actions, obs, None if is_eval else refs[t], seqs[t], live.ptr(t),
                  None if is_eval or side is not None else refs[t + 1])
 
         warm = torch.cuda.Stream(dev)            # the student's libraries warmed off the capture
@@ -377,25 +365,62 @@ def _same_act(ref, act):
     return cached is not None and cached == act
 
 
-def _live_flags(sim, T):
-    """The per-tick any-live flags of do_rollout: a page-locked host int32 array (zeroed here,
-    reused across rollouts: the previous rollout's ticks have completed when it returned), its
-    device address (craft_host_flag_pointer) or 0 where HIP does not map it, and one event per
-    tick."""
-    flags = getattr(sim, "_live_host", None)
-    if sim._cpu and (flags is None or flags.numel() < T + 1):
-        # the CPU variant's "device" memory is the host's, and its calls have completed on return
-        flags = sim._live_host = torch.zeros(max(T + 1, 64), dtype=torch.int32)
-        sim._live_events = [_NoEvent()] * flags.numel()
-        sim._live_dev = flags.data_ptr()
-    elif flags is None or flags.numel() < T + 1:
-        flags = sim._live_host = torch.zeros(max(T + 1, 64), dtype=torch.int32, pin_memory=True)
-        sim._live_events = [torch.cuda.Event() for _ in range(flags.numel())]
-        p = ctypes.c_void_p()
-        ok = N.lib().craft_host_flag_pointer(flags.data_ptr(), ctypes.byref(p)) == 0
-        sim._live_dev = p.value if ok and p.value else 0
-    flags[:T + 1].zero_()
-    return flags, sim._live_dev, sim._live_events
+def _actions(a, n, dev):
+    """The student's actions as an int32 [n] device tensor (one that already is: itself, no
+    device work)."""
+    if not torch.is_tensor(a):
+        a = torch.as_tensor(np.asarray(a), device=dev)
+    return a.to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+
+
+def _teacher_stream(sim):
+    """The side stream the unfused teacher runs on, created once per simulator (costly)."""
+    side = getattr(sim, "_teacher_stream", None)
+    if side is None:
+        side = sim._teacher_stream = torch.cuda.Stream(sim.device)
+    return side
+
+
+class _LiveFlags:
+    """The any-live flags of a driver's ticks (1: some env still running after tick t), one per
+    tick: a page-locked host int32 array (`host`; zeroed here, reused across rollouts: the
+    previous rollout's ticks have completed when it returned) that the kernel stores into
+    directly where HIP maps it (`dev`, its device address from craft_host_flag_pointer), else
+    (`dev` 0) a device array copied back per tick; and one event per tick (`events`).  The three
+    are cached on the simulator as _live_host, _live_dev and _live_events."""
+
+    def __init__(self, sim, T):
+        flags = getattr(sim, "_live_host", None)
+        if sim._cpu and (flags is None or flags.numel() < T + 1):
+            # the CPU variant's "device" memory is the host's, and its calls have completed on return
+            flags = sim._live_host = torch.zeros(max(T + 1, 64), dtype=torch.int32)
+            sim._live_events = [_NoEvent()] * flags.numel()
+            sim._live_dev = flags.data_ptr()
+        elif flags is None or flags.numel() < T + 1:
+            flags = sim._live_host = torch.zeros(max(T + 1, 64), dtype=torch.int32, pin_memory=True)
+            sim._live_events = [torch.cuda.Event() for _ in range(flags.numel())]
+            p = ctypes.c_void_p()
+            ok = N.lib().craft_host_flag_pointer(flags.data_ptr(), ctypes.byref(p)) == 0
+            sim._live_dev = p.value if ok and p.value else 0
+        flags[:T + 1].zero_()
+        self.host, self.dev, self.events = flags, sim._live_dev, sim._live_events
+        self.live = None if self.dev else torch.zeros(T + 1, dtype=torch.int32, device=sim.device)
+
+    def ptr(self, t):
+        """Where tick t's kernel stores its flag (the tick's any_live argument)."""
+        return self.dev + 4 * t if self.dev else self.live[t].data_ptr()
+
+    def record(self, t):
+        """After tick t's launch: the flag's copy to the host where it is not mapped, then the
+        tick's event."""
+        if not self.dev:
+            self.host[t:t + 1].copy_(self.live[t:t + 1], non_blocking=True)
+        self.events[t].record()
+
+    def wait(self, t):
+        """Blocks until tick t's event has completed; True while some env is still running."""
+        self.events[t].synchronize()
+        return int(self.host[t]) != 0
 
 
 class _NoEvent:
@@ -408,6 +433,22 @@ class _NoEvent:
         pass
 
 
+def _distances(sim, task, success, seqs, flags_out):
+    """craft_rollout_distances over the rollout's final states: every env's distance, is_get
+    (bool) and action count, device tensors [n]; flags_out (two int32 on the device) receives
+    the None-success and unreachable-target flags."""
+    n, dev = sim.n_envs, sim.device
+    task = task.contiguous()
+    distances = torch.empty(n, dtype=torch.int32, device=dev)
+    is_get = torch.empty(n, dtype=torch.uint8, device=dev)
+    n_actions = torch.empty(n, dtype=torch.int32, device=dev)
+    sim._check(sim._L.craft_rollout_distances(
+        sim._h, task.data_ptr(), success.data_ptr(), seqs.data_ptr(), seqs.shape[0],
+        distances.data_ptr(), is_get.data_ptr(), n_actions.data_ptr(), flags_out.data_ptr(),
+        sim._stream()), "craft_rollout_distances")
+    return distances, is_get.view(torch.bool), n_actions
+
+
 def _finish(sim, task, success, seqs, t, is_eval, keep_obs, obs_hist, timing, t_start, t_loop,
             t_end_loop, dev):
     """The rollout's summary (imitation.py:79-99) with one read-back: one launch computes every
@@ -415,18 +456,10 @@ def _finish(sim, task, success, seqs, t, is_eval, keep_obs, obs_hist, timing, t_
     final pose), is_get and action count (craft_rollout_distances); then the episode counters,
     the None-success and unreachable-target flags and the latched-error word come back in one
     transfer."""
-    n = sim.n_envs
-    task = task.contiguous()
     buf = getattr(sim, "_summary_buf", None)
     if buf is None:   # int64 [0:3] stats, [3] the two flags (int32), [4:6] the error word (int32[4])
         buf = sim._summary_buf = torch.zeros(6, dtype=torch.int64, device=dev)
-    distances = torch.empty(n, dtype=torch.int32, device=dev)
-    is_get = torch.empty(n, dtype=torch.uint8, device=dev)
-    n_actions = torch.empty(n, dtype=torch.int32, device=dev)
-    sim._check(sim._L.craft_rollout_distances(
-        sim._h, task.data_ptr(), success.data_ptr(), seqs.data_ptr(), seqs.shape[0],
-        distances.data_ptr(), is_get.data_ptr(), n_actions.data_ptr(), buf[3:4].data_ptr(),
-        sim._stream()), "craft_rollout_distances")
+    distances, is_get, n_actions = _distances(sim, task, success, seqs, buf[3:4])
     sim.stats(out=buf[0:3])
     sim.error_word(out=buf[4:6].view(torch.int32))
     summary = buf.cpu()
@@ -440,7 +473,6 @@ def _finish(sim, task, success, seqs, t, is_eval, keep_obs, obs_hist, timing, t_
         raise RolloutError("satisfies() returned None for a finished episode (imitation.py:68)")
     if unreachable:
         raise RolloutError("find_closest_resources found no target: len(None) (imitation.py:88-89)")
-    is_get = is_get.view(torch.bool)
     num_interactions = 0 if is_eval else env_steps
     num_steps = 0 if is_eval else env_steps - ended
     if timing is not None:
@@ -464,7 +496,7 @@ class EvalContext:
         self.episode, self.tick, self.restarted = episode, tick, restarted
 
 
-class EvalInfo:
+class EvalInfo(_Info):
     """ImitationTrainer.evaluate's results (trainers/imitation.py:183-226): eval_info, the
     reference's dict id -> {'actions', 'success'}; success_rate (per cent) and avg_distance
     (get tasks only) as it logs them; and per instance, in the order of `specs`, host arrays:
@@ -472,8 +504,58 @@ class EvalInfo:
     distances int32 (-1 where the task is not a get task), end_pose int32 [count, 3] (x, y,
     dir of the final state); ticks = step launches of the pass."""
 
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+
+def _specs_array(specs):
+    """A pass's `specs`, the (scenario, x, y, dir, task) arrays or [count, 5] rows, as a
+    contiguous int32 host array [count >= 1, 5]."""
+    specs = np.ascontiguousarray(np.asarray(torch.as_tensor(_stack_specs(specs)).cpu()),
+                                 dtype=np.int32)
+    if specs.ndim != 2 or specs.shape[1] != 5 or len(specs) == 0:
+        raise ValueError("specs must be [count >= 1, 5]")
+    return specs
+
+
+def _begin_pass(sim, specs, obs=None):
+    """Starts one pass over `specs` (a _specs_array): installs them as the episode queue and
+    puts slot i on row i, to take rows i + n, i + 2n, ... after it.  Every slot needs a first
+    entry, so a split shorter than n_envs is padded with copies of its first row, whose episodes
+    the results drop.  Returns the padded queue, count = len(specs) and Q = len(queue)."""
+    n, count = sim.n_envs, len(specs)
+    queue = specs if count >= n else np.concatenate([specs, np.repeat(specs[:1], n - count, 0)])
+    sim.set_episode_queue(torch.as_tensor(queue))
+    sim.begin_episodes(first=0, stride=n, wrap=False, obs=obs)
+    return queue, count, len(queue)
+
+
+def _pose_xyd(p):
+    """end_pose words (x | y << 8 | dir << 16) as (x, y, dir)."""
+    return p & 0xff, (p >> 8) & 0xff, (p >> 16) & 3
+
+
+def _cut_episodes(ended, pose, succ, count, rec=None, T=None):
+    """A pass's per-tick records, host arrays [ticks, n] (the queue index of an episode that
+    ended at that tick in that slot or -1, its final pose word, its success; rec: the action
+    taken), as per-episode results in the order of the queue: length int32 [count], success int8
+    [count] (-2: never finished), end_pose int32 [count, 3] and, with rec, the actions int32
+    [count, T] padded with -1 (else None).  Slot i runs episodes i, i + n, ... in order, so an
+    episode's ticks are those after the slot's previous end, up to its own.  Rows >= count
+    (the padding of a short split) are dropped."""
+    length = np.zeros(count, dtype=np.int32)
+    success = np.full(count, -2, dtype=np.int8)
+    end_pose = np.zeros((count, 3), dtype=np.int32)
+    seqs = None if rec is None else np.full((count, T), -1, dtype=np.int32)
+    tt, ii = np.nonzero(ended >= 0)
+    start = np.zeros(ended.shape[1], dtype=np.int64)
+    for t, i in zip(tt, ii):                             # (np.nonzero: tick-major, so in order per slot)
+        e = ended[t, i]
+        if e < count:
+            length[e] = t + 1 - start[i]
+            success[e] = succ[t, i]
+            end_pose[e] = _pose_xyd(pose[t, i])
+            if rec is not None:
+                seqs[e, :length[e]] = rec[start[i]:t + 1, i]
+        start[i] = t + 1
+    return length, success, end_pose, seqs
 
 
 def evaluate(sim, specs, act, ids=None, max_ticks=None):
@@ -501,24 +583,14 @@ def _queue_pass(sim, specs, act, ids, max_ticks, lang):
     trainer's), or with `lang` craft_step_lang_stream (the language trainers':
     language_rollout.evaluate).  The two argument structs name their shared fields alike."""
     n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
-    if isinstance(specs, (tuple, list)) and len(specs) == 5 and np.ndim(specs[0]) == 1:
-        specs = np.stack([np.asarray(torch.as_tensor(a).cpu()) for a in specs], 1)
-    specs = np.ascontiguousarray(np.asarray(torch.as_tensor(specs).cpu()), dtype=np.int32)
-    if specs.ndim != 2 or specs.shape[1] != 5 or len(specs) == 0:
-        raise ValueError("specs must be [count >= 1, 5]")
-    count = len(specs)
-    ids = list(range(count)) if ids is None else list(ids)
-    if len(ids) != count:
-        raise ValueError(f"{len(ids)} ids for {count} specs")
-    # every slot needs a first entry: a short split is padded with copies of its first row,
-    # whose episodes are dropped
-    queue = specs if count >= n else np.concatenate([specs, np.repeat(specs[:1], n - count, 0)])
-    rounds = (len(queue) + n - 1) // n
-    bound = rounds * T
-    max_ticks = bound if max_ticks is None else min(int(max_ticks), bound)
-    sim.set_episode_queue(torch.as_tensor(queue))
+    specs = _specs_array(specs)
+    ids = list(range(len(specs))) if ids is None else list(ids)
+    if len(ids) != len(specs):
+        raise ValueError(f"{len(ids)} ids for {len(specs)} specs")
     obs = sim.empty_obs()
-    sim.begin_episodes(first=0, stride=n, wrap=False, obs=obs)
+    _, _, Q = _begin_pass(sim, specs, obs)
+    bound = -(-Q // n) * T                                # no slot's stream of episodes is longer
+    max_ticks = bound if max_ticks is None else min(int(max_ticks), bound)
     i32 = dict(dtype=torch.int32, device=dev)
     rec = torch.full((max_ticks, n), -1, **i32)
     ended = torch.full((max_ticks, n), -1, **i32)
@@ -526,8 +598,7 @@ def _queue_pass(sim, specs, act, ids, max_ticks, lang):
     succ = torch.full((max_ticks, n), -1, dtype=torch.int8, device=dev)
     now = torch.empty(n, **i32)
     ctx = EvalContext(torch.arange(n, **i32), torch.zeros(n, **i32), torch.ones(n, **i32))
-    flags, flag_dev, events = _live_flags(sim, max_ticks)
-    live = None if flag_dev else torch.zeros(max_ticks + 1, **i32)
+    live = _LiveFlags(sim, max_ticks)
     what = "craft_step_lang_stream" if lang else "craft_step_stream"
     args = N.craft_lang_stream_step_args_t() if lang else N.craft_stream_step_args_t()
     args.step.flags = 0 if lang else N.STEP_AUTORESET
@@ -537,15 +608,12 @@ def _queue_pass(sim, specs, act, ids, max_ticks, lang):
     t = 0
     running = True
     while running and t < max_ticks:
-        actions = act(obs, ctx)
-        if not torch.is_tensor(actions):
-            actions = torch.as_tensor(np.asarray(actions), device=dev)
-        actions = actions.to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+        actions = _actions(act(obs, ctx), n, dev)
         args.step.actions = actions.data_ptr()
         args.step.tick = t
         args.step.success = succ[t].data_ptr()
         args.step.action_record = rec[t].data_ptr()
-        args.step.any_live = flag_dev + 4 * t if flag_dev else live[t].data_ptr()
+        args.step.any_live = live.ptr(t)
         args.episode_end = ended[t].data_ptr()
         args.end_pose = pose[t].data_ptr()
         st = fn(h, pargs, sim._stream())
@@ -555,11 +623,8 @@ def _queue_pass(sim, specs, act, ids, max_ticks, lang):
         began = ended[t] >= 0
         ctx = EvalContext(now.clone(), torch.where(began, 0, ctx.tick + 1).to(torch.int32),
                           (began & (now >= 0)).to(torch.int32))
-        if not flag_dev:
-            flags[t:t + 1].copy_(live[t:t + 1], non_blocking=True)
-        events[t].record()
-        events[t].synchronize()
-        running = int(flags[t]) != 0
+        live.record(t)
+        running = live.wait(t)
         t += 1
     if running:
         raise RuntimeError(f"evaluate: slots still running after {t} ticks")
@@ -577,23 +642,7 @@ def _eval_summary(sim, specs, ids, rec, ended, pose, succ, ticks, lines):
     pose is the final state's (the language protocol's: after the ending step).  lines: where
     the reference raises, for the two messages."""
     n, T, count = sim.n_envs, sim.config.max_timesteps, len(specs)
-    seqs = np.full((count, T), -1, dtype=np.int32)
-    n_actions = np.zeros(count, dtype=np.int32)
-    success = np.full(count, -2, dtype=np.int8)          # -2: never finished
-    end_pose = np.zeros((count, 3), dtype=np.int32)
-    # slot i runs episodes i, i + n, ... in order: cut its action column at its episode ends
-    tt, ii = np.nonzero(ended >= 0)
-    start = np.zeros(n, dtype=np.int64)
-    for t, i in zip(tt, ii):                             # (np.nonzero: tick-major, so in order per slot)
-        e = ended[t, i]
-        if e < count:
-            a = rec[start[i]:t + 1, i]
-            seqs[e, :len(a)] = a
-            n_actions[e] = len(a)
-            success[e] = succ[t, i]
-            p = pose[t, i]
-            end_pose[e] = (p & 0xff, (p >> 8) & 0xff, (p >> 16) & 3)
-        start[i] = t + 1
+    n_actions, success, end_pose, seqs = _cut_episodes(ended, pose, succ, count, rec, T)
     if (success == -2).any():
         raise RuntimeError(f"evaluate: instance {int(np.argmax(success == -2))} was never finished")
     if (success < 0).any():
@@ -632,13 +681,10 @@ def _eval_summary(sim, specs, ids, rec, ended, pose, succ, ticks, lines):
                     is_get=is_get, end_pose=end_pose, ticks=ticks)
 
 
-class ReplayInfo:
+class ReplayInfo(_Info):
     """replay()'s results, host arrays in the order of `specs`: success int8 (satisfies() of the
     state the episode ended in), length int32 (ticks the device ran the episode for), end_pose
     int32 [count, 3] (x, y, dir of the final state); ticks and launches of the pass."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
 
 def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
@@ -666,14 +712,9 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
     K = int(ticks_per_launch)
     if K < 1:
         raise ValueError("ticks_per_launch must be >= 1")
-    if isinstance(specs, (tuple, list)) and len(specs) == 5 and np.ndim(specs[0]) == 1:
-        specs = np.stack([np.asarray(torch.as_tensor(a).cpu()) for a in specs], 1)
-    specs = np.ascontiguousarray(np.asarray(torch.as_tensor(specs).cpu()), dtype=np.int32)
-    if specs.ndim != 2 or specs.shape[1] != 5 or len(specs) == 0:
-        raise ValueError("specs must be [count >= 1, 5]")
-    count = len(specs)
-    if len(action_seqs) != count:
-        raise ValueError(f"{len(action_seqs)} action sequences for {count} specs")
+    specs = _specs_array(specs)
+    if len(action_seqs) != len(specs):
+        raise ValueError(f"{len(action_seqs)} action sequences for {len(specs)} specs")
     seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in action_seqs]
     for e, s in enumerate(seqs):
         if len(s) > T:
@@ -685,12 +726,9 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
             raise ValueError(f"episode {e}: STOP at step {int(stops[0])}, before its end")
         if not len(stops) and len(s) != T:
             raise ValueError(f"episode {e}: {len(s)} actions without a STOP (max_timesteps is {T})")
-    # every slot needs a first entry: a short split is padded with copies of its first row that
-    # STOP at once, whose episodes are dropped
-    pad = max(0, n - count)
-    queue = specs if not pad else np.concatenate([specs, np.repeat(specs[:1], pad, 0)])
-    seqs = seqs + [np.asarray([N.STOP], dtype=np.int64)] * pad
-    Q = len(queue)
+    obs0 = sim.empty_obs()
+    _, count, Q = _begin_pass(sim, specs, obs0)
+    seqs = seqs + [np.asarray([N.STOP], dtype=np.int64)] * (Q - count)   # the padding STOPs at once
     length = np.asarray([len(s) for s in seqs], dtype=np.int64)
     off = np.concatenate([[0], np.cumsum(length)])[:-1]
     flat = np.concatenate(seqs).astype(np.int32)
@@ -699,9 +737,6 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
     np.add.at(per_slot, np.arange(Q) % n, length)
     total = int(per_slot.max())
 
-    sim.set_episode_queue(torch.as_tensor(queue))
-    obs0 = sim.empty_obs()
-    sim.begin_episodes(first=0, stride=n, wrap=False, obs=obs0)
     i32 = dict(dtype=torch.int32, device=dev)
     ring = torch.empty((K, n, sim.n_features), dtype=sim.obs_dtype, device=dev)
     ended = torch.empty((K, n), **i32)
@@ -724,10 +759,7 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
     if on_chunk is not None:
         on_chunk(obs0[None], torch.as_tensor(shown(ep), **i32)[None], torch.zeros((1, n), **i32),
                  torch.as_tensor(shown(next_action(-1)), **i32)[None])
-    success = np.full(count, -2, dtype=np.int8)
-    ran = np.full(count, -1, dtype=np.int32)
-    end_pose = np.zeros((count, 3), dtype=np.int32)
-    last_end = np.full(n, -1, dtype=np.int64)
+    rows = {k: [] for k in ("ended", "pose", "succ")}
     t0 = launches = 0
     while True:
         k = min(K, total - t0)
@@ -749,27 +781,20 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
         sim.rollout_stream(k, tick0=t0, actions=torch.as_tensor(acts).to(dev), obs=ring, success=succ,
                            episode_end=ended, end_pose=pose, episode_now=now)
         launches += 1
-        ee, pp, ss, nn = (x[:k].cpu().numpy() for x in (ended, pose, succ, now))
-        for j in range(k):
-            i = np.nonzero(ee[j] >= 0)[0]
-            e = ee[j, i]
-            keep = e < count
-            i, e = i[keep], e[keep]
-            ran[e] = t0 + j - last_end[i]
-            success[e] = ss[j, i]
-            p = pp[j, i]
-            end_pose[e] = np.stack([p & 0xff, (p >> 8) & 0xff, (p >> 16) & 3], 1)
-            last_end[np.nonzero(ee[j] >= 0)[0]] = t0 + j
+        for key, x in (("ended", ended), ("pose", pose), ("succ", succ)):
+            rows[key].append(x[:k].cpu().numpy().copy())
         if on_chunk is not None:
             episode = torch.where(now[:k] >= count, -1, now[:k]).to(torch.int32)
             on_chunk(ring[:k], episode, torch.as_tensor(c_st, **i32), torch.as_tensor(c_act, **i32))
         t0 += k
-        if (nn[k - 1] < 0).all():
+        if (now[k - 1].cpu().numpy() < 0).all():
             break
     try:
         sim.check()                                      # an error latched during the pass
     except N.CraftError as e:
         raise RolloutError(f"replay: {e}") from e
+    ran, success, end_pose, _ = _cut_episodes(*(np.concatenate(rows[k]) for k in
+                                                ("ended", "pose", "succ")), count)
     bad = np.nonzero(ran != length[:count])[0]
     if len(bad):
         e = int(bad[0])
@@ -778,14 +803,11 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
     return ReplayInfo(success=success, length=ran, end_pose=end_pose, ticks=t0, launches=launches)
 
 
-class DemonstrationInfo:
+class DemonstrationInfo(_Info):
     """demonstrations()'s results, host arrays in the order of `specs`: action_seqs int32
     [count, max_timesteps] (each episode's actions, its STOP included, padded with -1), length
     int32, success int8 (satisfies() of the state the episode ended in), end_pose int32
     [count, 3] (x, y, dir of the final state); ticks and launches of the pass."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
     def actions(self, e):
         """Episode e's action sequence as a list of ints."""
@@ -805,21 +827,8 @@ def demonstrations(sim, specs, ticks_per_launch=32):
     K = int(ticks_per_launch)
     if K < 1:
         raise ValueError("ticks_per_launch must be >= 1")
-    if isinstance(specs, (tuple, list)) and len(specs) == 5 and np.ndim(specs[0]) == 1:
-        specs = np.stack([np.asarray(torch.as_tensor(a).cpu()) for a in specs], 1)
-    specs = np.ascontiguousarray(np.asarray(torch.as_tensor(specs).cpu()), dtype=np.int32)
-    if specs.ndim != 2 or specs.shape[1] != 5 or len(specs) == 0:
-        raise ValueError("specs must be [count >= 1, 5]")
-    count = len(specs)
-    # every slot needs a first entry: a short list is padded with copies of its first row, whose
-    # episodes are dropped
-    pad = max(0, n - count)
-    queue = specs if not pad else np.concatenate([specs, np.repeat(specs[:1], pad, 0)])
-    Q = len(queue)
+    _, count, Q = _begin_pass(sim, _specs_array(specs))
     bound = -(-Q // n) * T                                # no slot's stream of episodes is longer
-
-    sim.set_episode_queue(torch.as_tensor(queue))
-    sim.begin_episodes(first=0, stride=n, wrap=False)
     label_in, _ = sim.teacher()
     i32 = dict(dtype=torch.int32, device=dev)
     labels = torch.empty((K, n), **i32)
@@ -862,27 +871,10 @@ def demonstrations(sim, specs, ticks_per_launch=32):
     if first_raise is not None:
         raise RolloutError(f"demonstrations: the teacher raised on instance {first_raise}")
 
-    seqs = np.full((count, T), -1, dtype=np.int32)
-    length = np.zeros(count, dtype=np.int32)
-    success = np.full(count, -2, dtype=np.int8)          # -2: never finished
-    end_pose = np.zeros((count, 3), dtype=np.int32)
-    stopped = np.zeros(count, dtype=bool)
-    # slot i runs instances i, i + n, ... in order: cut its action column at its episode ends
-    tt, ii = np.nonzero(ended >= 0)
-    start = np.zeros(n, dtype=np.int64)
-    for t, i in zip(tt, ii):                             # (np.nonzero: tick-major, so in order per slot)
-        e = ended[t, i]
-        if e < count:
-            a = rec[start[i]:t + 1, i]
-            seqs[e, :len(a)] = a
-            length[e] = len(a)
-            success[e] = succ[t, i]
-            stopped[e] = a[-1] == N.STOP
-            p = pose[t, i]
-            end_pose[e] = (p & 0xff, (p >> 8) & 0xff, (p >> 16) & 3)
-        start[i] = t + 1
+    length, success, end_pose, seqs = _cut_episodes(ended, pose, succ, count, rec, T)
     if (success == -2).any():
         raise RolloutError(f"demonstrations: instance {int(np.argmax(success == -2))} was never finished")
+    stopped = seqs[np.arange(count), length - 1] == N.STOP
     wrong = ~stopped | (success != 1)
     if wrong.any():
         e = int(np.argmax(wrong))

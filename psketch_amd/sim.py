@@ -52,6 +52,14 @@ def _ring_extent(named_outputs, n):
     return ring
 
 
+def _stack_specs(specs):
+    """The 5-tuple of arrays Dataset.specs returns as one host [count, 5] array; anything else
+    as it came."""
+    if isinstance(specs, (tuple, list)) and len(specs) == 5 and np.ndim(specs[0]) == 1:
+        return np.stack([np.asarray(torch.as_tensor(a).cpu()) for a in specs], 1)
+    return specs
+
+
 class CraftSim:
     """N CraftWorld environments on one GPU.
 
@@ -445,10 +453,7 @@ class CraftSim:
         (scenario, x0, y0, dir0, task), or the 5-tuple of arrays Dataset.specs returns.  Every
         entry is checked on the device; an invalid one raises (EINVAL, naming the first) and
         the queue installed before stays.  Synchronous."""
-        if isinstance(specs, (tuple, list)) and len(specs) == 5 and not np.isscalar(specs[0]) \
-                and np.ndim(specs[0]) == 1:
-            specs = np.stack([np.asarray(torch.as_tensor(a).cpu()) for a in specs], 1)
-        q = torch.as_tensor(specs)
+        q = torch.as_tensor(_stack_specs(specs))
         if q.dim() != 2 or q.shape[1] != 5:
             raise ValueError(f"specs must be [count, 5], got {tuple(q.shape)}")
         q = q.to(device=self.device, dtype=torch.int32).contiguous()
