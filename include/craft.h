@@ -632,6 +632,71 @@ typedef struct {
 } craft_rollout_teach_stream_args_t;
 int craft_rollout_teach_stream(craft_sim_t* sim, const craft_rollout_teach_stream_args_t* args, void* stream);
 
+/* The per-episode results of a queue pass: turns the per-tick records of craft_step_stream,
+ * craft_step_lang_stream, craft_rollout_stream or craft_rollout_teach_stream ([ticks][n_envs]
+ * rows in tick order, as those entry points write them) into results indexed by queue entry,
+ * what ImitationTrainer.evaluate and the training log report (trainers/imitation.py:79-91,
+ * 183-226).  Reads the installed queue, the pool and the teacher table; touches no slot state
+ * (state, inventory, cleared cells, cursors, statistics) and does not need craft_episode_begin.
+ * Per slot i, in tick order, with a running count that starts at run[i] (0 without run): for
+ * every tick t with e = episode_end[t][i] >= 0 the slot's episode ends.  e >= count (the padding
+ * of a short split) is skipped; e >= the queue's length is skipped and latches CRAFT_ERANGE with
+ * the slot, as does any episode_end value < -1 (which is no end).  Otherwise
+ *   length_out[e]   = ticks since the slot's previous end, or since the episode began run[i]
+ *                     ticks before row 0, the ending tick included;
+ *   success_out[e]  = success[t][i]; flags_out[0] = 1 when that is < 0 (imitation.py:68);
+ *   end_pose_out[e] = end_pose[t][i];
+ *   actions_out[e]  = the action_record entries of exactly those ticks (at positions run[i] + k
+ *                     for an episode that began before row 0: the calls before wrote the earlier
+ *                     ones), then -1 up to max_timesteps; positions >= max_timesteps are dropped
+ *                     while length_out keeps the true count;
+ *   distance_out[e] = what craft_rollout_distances documents for (the entry's task, that
+ *                     success, that pose) on the entry's pool row with nothing cleared: -1 for
+ *                     goals other than `get`, 0 for a get that did not fail, else the path
+ *                     length; -1 where find_closest_resources returns None (the grid holds no
+ *                     target, or none of them can be reached) and -2 where it raises (an
+ *                     unreachable target after a reachable one, base.py:31), both setting
+ *                     flags_out[1] and latching nothing; a pose outside the interior latches
+ *                     CRAFT_EINVAL with the slot and gives -2.
+ * After the last row, with run: run[i] = the ticks of the still-running episode, 0 for a slot
+ * that has run out (episode_now[i] < 0, where episode_now is given); with run and actions_out the
+ * running episode's actions so far are written at their positions in row episode_now[i] when that
+ * is in [0, count), and the call over the next launch's records completes the row.
+ * Entries for which the records hold no end are left untouched: the caller pre-fills them.  With
+ * CRAFT_QUEUE_WRAP an entry may end more than once within one call; its outputs are then those
+ * of one of the ends, unspecified which (the HIP library: each output array holds one end's
+ * value, and distance_out is the distance of the success_out and end_pose_out it left).
+ * flags_out is only ever set to 1, by plain stores, and never zeroed here.  ticks == 0 is a
+ * no-op.  Stream-ordered; allocates nothing.
+ * CRAFT_EINVAL, tested in this order, before any work: args NULL; a NULL episode_end, end_pose,
+ * success, length_out, success_out, end_pose_out or flags_out; ticks < 0; no queue installed;
+ * count outside 1 .. the queue's length; actions_out without action_record; run with
+ * action_record but without episode_now; with distance_out, the BFS-queue limit (4*W*H > 1000);
+ * and (the HIP library, with distance_out) a launch under stream capture while pool rows wait for
+ * their teacher-table entries (craft_sim_sync_table first).
+ * Two launches in the HIP library: one lane per slot scans its record column; then, with
+ * distance_out, lane pairs or quads per queue entry run the BFS of the failed get episodes the
+ * teacher table did not answer (DESIGN.md "The per-episode summary of a queue pass"). */
+typedef struct {
+  const int32_t* episode_end;    /* device int32[ticks][n_envs], as the stream entry points write it */
+  const int32_t* end_pose;       /* int32[ticks][n_envs] */
+  const int8_t*  success;        /* int8 [ticks][n_envs] */
+  const int32_t* action_record;  /* int32[ticks][n_envs], or NULL */
+  int32_t  ticks;                /* rows of the records; 0 is a no-op */
+  int32_t* run;                  /* int32[n_envs] in/out, or NULL (= all zero, nothing written back):
+                                    ticks each slot's current episode had already run before row 0 */
+  const int32_t* episode_now;    /* int32[n_envs]: the episode_now row of the records' LAST tick;
+                                    required when run and action_record are both set */
+  int64_t  count;                /* outputs cover queue entries [0, count), 1 <= count <= queue length */
+  int32_t* length_out;           /* int32[count]: ticks the episode ran, its ending tick included */
+  int8_t*  success_out;          /* int8 [count] */
+  int32_t* end_pose_out;         /* int32[count]: the x | y << 8 | dir << 16 word */
+  int32_t* distance_out;         /* int32[count], or NULL: no BFS runs */
+  int32_t* actions_out;          /* int32[count][max_timesteps], or NULL; needs action_record */
+  int32_t* flags_out;            /* int32[2], only ever set to 1 by plain stores, never zeroed here */
+} craft_episode_summary_args_t;
+int craft_episode_summary(craft_sim_t* sim, const craft_episode_summary_args_t* args, void* stream);
+
 /* Sums the episode statistics accumulated by craft_step into stats_out
  * (device int64[3] = {successes, episodes ended, env-steps}) — the scalar
  * summary a multi-GPU run all-reduces over RCCL.  reset != 0 zeroes the

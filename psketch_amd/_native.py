@@ -183,6 +183,25 @@ class craft_rollout_teach_stream_args_t(ctypes.Structure):
     ]
 
 
+class craft_episode_summary_args_t(ctypes.Structure):
+    _fields_ = [
+        ("episode_end", ctypes.c_void_p),
+        ("end_pose", ctypes.c_void_p),
+        ("success", ctypes.c_void_p),
+        ("action_record", ctypes.c_void_p),
+        ("ticks", ctypes.c_int32),
+        ("run", ctypes.c_void_p),
+        ("episode_now", ctypes.c_void_p),
+        ("count", ctypes.c_int64),
+        ("length_out", ctypes.c_void_p),
+        ("success_out", ctypes.c_void_p),
+        ("end_pose_out", ctypes.c_void_p),
+        ("distance_out", ctypes.c_void_p),
+        ("actions_out", ctypes.c_void_p),
+        ("flags_out", ctypes.c_void_p),
+    ]
+
+
 OBS_F32, OBS_BF16, OBS_U8 = 0, 1, 2
 
 _vp = ctypes.c_void_p
@@ -231,6 +250,7 @@ SIGNATURES = {
     "craft_rollout_stream": (_i32, [_vp, ctypes.POINTER(craft_rollout_stream_args_t), _vp]),
     "craft_rollout_teach": (_i32, [_vp, ctypes.POINTER(craft_rollout_teach_args_t), _vp]),
     "craft_rollout_teach_stream": (_i32, [_vp, ctypes.POINTER(craft_rollout_teach_stream_args_t), _vp]),
+    "craft_episode_summary": (_i32, [_vp, ctypes.POINTER(craft_episode_summary_args_t), _vp]),
     "craft_stats": (_i32, [_vp, _vp, _i32, _vp]),
     "craft_transition": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "craft_observe": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),

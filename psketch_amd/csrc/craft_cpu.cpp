@@ -24,10 +24,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "craft_checks_episode_summary.h"
 #include "craft_checks_lang_stream.h"
 #include "craft_checks_rollout_stream.h"
 #include "craft_checks_rollout_teach_stream.h"
@@ -1521,6 +1523,96 @@ int craft_rollout_distances(craft_sim_t* s, const int32_t* tasks, const int8_t* 
   });
   flags_out[0] = f0.load();
   flags_out[1] = f1.load();
+  return CRAFT_OK;
+}
+
+// The per-episode results of a queue pass, written out on its own like the rest of this library:
+// each worker walks its slots' record columns in tick order.  With CRAFT_QUEUE_WRAP two slots may
+// end the same entry within one call, so an entry's outputs are written together under one of a
+// few striped locks: a result is one end's, never a mix of two.
+int craft_episode_summary(craft_sim_t* s, const craft_episode_summary_args_t* x, void* /*stream*/) {
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_episode_summary(facts(s), x, s->last_error)) return rc;
+  if (x->ticks == 0) return CRAFT_OK;
+  const int64_t n = s->n_envs, qlen = (int64_t)s->queue.size(), count = x->count;
+  const int T = s->cfg.max_timesteps, ticks = x->ticks;
+  constexpr int kLocks = 64;
+  std::mutex locks[kLocks];
+  std::atomic<int32_t> f0{0}, f1{0};
+  parallel_for(s, n, [&](int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i) {
+      // the running episode: cnt ticks so far; its first tick within the records is row `start`,
+      // which is its action number `base` (run[i] until the slot's first end, then 0)
+      int base = x->run ? std::max(x->run[i], 0) : 0;
+      int cnt = base, start = 0;
+      // the records' actions of rows [start, end) as positions [base, ...) of a row of actions_out
+      auto put_actions = [&](int32_t* row, int end) {
+        for (int k = start; k < end && base + (k - start) < T; ++k)
+          row[base + (k - start)] = x->action_record[(int64_t)k * n + i];
+      };
+      for (int t = 0; t < ticks; ++t) {
+        ++cnt;
+        const int32_t e = x->episode_end[(int64_t)t * n + i];
+        if (e < 0) {
+          if (e < -1) latch(s, CRAFT_ERANGE, i);
+          continue;
+        }
+        if (e >= qlen) {
+          latch(s, CRAFT_ERANGE, i);
+        } else if (e < count) {
+          const int succ = x->success[(int64_t)t * n + i];
+          const int32_t pose = x->end_pose[(int64_t)t * n + i];
+          int d = 0;
+          if (x->distance_out) {                       // craft_rollout_distances' rule, trainers/imitation.py:79-91
+            const craft_sim::QueueEntry& q = s->queue[(size_t)e];
+            const uint32_t tt = s->task_tab[q.task];
+            const bool is_get = (tt & 0xf) == CRAFT_GOAL_GET;
+            const int arg = (tt >> 4) & 0xff;
+            d = is_get ? 0 : -1;
+            if (is_get && succ == 0) {
+              const int px = pose & 0xff, py = (pose >> 8) & 0xff, pd = (pose >> 16) & 3;
+              if (arg == 0) {
+                d = -1;
+              } else if (pose < 0 || px < 1 || px > s->W - 2 || py < 1 || py > s->H - 2 || q.scen >= s->pool_count) {
+                latch(s, CRAFT_EINVAL, i);
+                d = -2;
+              } else {                                 // world.init_state(grid, pos, dir): the pool row
+                int fa = -1, len = -1;
+                const bool ok = closest(s, s->pool.data() + (size_t)q.scen * s->C, arg, px * s->H + py, pd, fa, len,
+                                        false);
+                d = ok ? len : -2;
+              }
+              if (d == -1 || d == -2) f1 = 1;          // len(None), imitation.py:88-89
+            }
+          }
+          if (succ < 0) f0 = 1;                        // satisfies() None, imitation.py:68
+          std::lock_guard<std::mutex> g(locks[e % kLocks]);
+          x->length_out[e] = cnt;
+          x->success_out[e] = (int8_t)succ;
+          x->end_pose_out[e] = pose;
+          if (x->distance_out) x->distance_out[e] = d;
+          if (x->actions_out) {
+            int32_t* row = x->actions_out + (int64_t)e * T;
+            put_actions(row, t + 1);
+            for (int p = cnt; p < T; ++p) row[p] = -1;
+          }
+        }
+        cnt = 0;
+        base = 0;
+        start = t + 1;
+      }
+      if (x->run) {
+        const int32_t now = x->episode_now ? x->episode_now[i] : 0;
+        x->run[i] = now < 0 ? 0 : cnt;
+        if (x->actions_out && now >= 0 && now < count) {   // the running episode's actions so far
+          std::lock_guard<std::mutex> g(locks[now % kLocks]);
+          put_actions(x->actions_out + (int64_t)now * T, ticks);
+        }
+      }
+    }
+  });
+  if (f0.load()) x->flags_out[0] = 1;
+  if (f1.load()) x->flags_out[1] = 1;
   return CRAFT_OK;
 }
 

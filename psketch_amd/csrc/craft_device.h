@@ -310,6 +310,25 @@ struct ScenarioArgs {      // craft_pool_generate
   int32_t* init_out;       // [count][2] or null
 };
 
+struct SummaryArgs {       // craft_episode_summary: the argument struct's pointers, and the queue
+  const int32_t* ep_end;   // [ticks][n_envs] records
+  const int32_t* end_pose;
+  const int8_t* success;
+  const int32_t* rec;      // or null
+  int32_t ticks;
+  int32_t* run;            // [n_envs] in/out, or null
+  const int32_t* ep_now;   // [n_envs], or null
+  const uint2* q_entries;  // the packed queue (TileArgs) and its length
+  int64_t q_len;
+  int64_t count;           // outputs cover entries [0, count)
+  int32_t* length_out;
+  int8_t* success_out;
+  int32_t* pose_out;
+  int32_t* dist_out;       // or null
+  int32_t* actions_out;    // [count][maxT], or null
+  int32_t* flags;          // [2]
+};
+
 struct Agent {
   int x, y, dir, frozen, timer, scen, task;
 };

@@ -42,6 +42,9 @@ hipError_t launch_distances(int nw, const SimView& v, const int32_t* tasks, cons
                             uint8_t* is_get_out, int32_t* n_actions_out, int32_t* flags, hipStream_t st);
 hipError_t launch_teach_table(int nw, const SimView& v, int32_t first, int32_t count, const int32_t* kinds,
                               hipStream_t st);
+// craft_episode_summary.hip: the scan over the slots' record columns, then (a.dist_out set) the
+// BFS of the entries the scan left pending
+hipError_t launch_episode_summary(int nw, const SimView& v, const SummaryArgs& a, hipStream_t st);
 // craft_scenarios.hip
 hipError_t launch_scenarios(const SimView& v, const ScenarioArgs& a, hipStream_t st);
 

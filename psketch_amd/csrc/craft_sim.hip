@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "craft_device.h"
+#include "craft_checks_episode_summary.h"
 #include "craft_checks_lang_stream.h"
 #include "craft_checks_rollout_stream.h"
 #include "craft_checks_rollout_teach_stream.h"
@@ -1208,6 +1209,27 @@ int craft_rollout_teach_stream(craft_sim_t* s, const craft_rollout_teach_stream_
                              return craft::launch_rollout_teach_stream(
                                  s->cfg.window_width, craft::teach_words(s->view.W, s->view.H), v, a, st);
                            });
+}
+
+int craft_episode_summary(craft_sim_t* s, const craft_episode_summary_args_t* x, void* stream) {
+  if (!s) return CRAFT_EINVAL;
+  int rc = craft_host::check_episode_summary(facts(s), x, s->last_error);
+  if (rc != CRAFT_OK) return rc;
+  if (x->ticks == 0) return CRAFT_OK;
+  // the scan reads the teacher table for the failed get episodes: the entries of newly loaded
+  // rows are built first
+  if (x->distance_out) {
+    rc = flush_table(s, stream, "craft_episode_summary");
+    if (rc != CRAFT_OK) return rc;
+  }
+  const craft::SummaryArgs a{x->episode_end, x->end_pose,   x->success,     x->action_record, x->ticks,
+                             x->run,         x->episode_now, s->d_queue,     s->q_count,       x->count,
+                             x->length_out,  x->success_out, x->end_pose_out, x->distance_out,  x->actions_out,
+                             x->flags_out};
+  const hipError_t e = craft::launch_episode_summary(craft::teach_words(s->view.W, s->view.H), teach_view(s), a,
+                                                     reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(s, e, "craft_episode_summary launch");
+  return CRAFT_OK;
 }
 
 int craft_stats(craft_sim_t* s, int64_t* stats_out, int32_t reset, void* stream) {

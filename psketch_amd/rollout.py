@@ -21,6 +21,7 @@ find_closest_resources' BFS), is_get and action count, and the summary comes bac
 transfer.
 """
 import ctypes
+import gc
 import inspect
 import time
 import weakref
@@ -572,8 +573,9 @@ def evaluate(sim, specs, act, ids=None, max_ticks=None):
     max_ticks: a bound on the pass (default: ceil(count / n) * max_timesteps, which it cannot
       exceed); RuntimeError if it ends with slots still running.
     The failed get episodes' distances (imitation.py:83-91: find_closest_resources on the
-    initial grid at the final pose) are computed after the pass, n_envs at a time, with
-    set_state + teacher(path_len_out=): the simulator's slots are overwritten.
+    initial grid at the final pose) are computed after the pass from the queue entries and the
+    recorded final poses (craft_episode_summary): the simulator's slots are left as the pass
+    left them.
     Raises RolloutError where the reference raises (success None; no reachable target)."""
     return _queue_pass(sim, specs, act, ids, max_ticks, lang=False)
 
@@ -629,49 +631,44 @@ def _queue_pass(sim, specs, act, ids, max_ticks, lang):
     if running:
         raise RuntimeError(f"evaluate: slots still running after {t} ticks")
     sim.check()                                  # an error latched during the pass
-    return _eval_summary(sim, specs, ids, rec[:t].cpu().numpy(), ended[:t].cpu().numpy(),
-                         pose[:t].cpu().numpy(), succ[:t].cpu().numpy(), t,
+    return _eval_summary(sim, specs, ids, rec[:t], ended[:t], pose[:t], succ[:t], t,
                          ("primitive_language.py:124", "primitive_language.py:129-131") if lang
                          else ("imitation.py:68", "imitation.py:88-89"))
 
 
 def _eval_summary(sim, specs, ids, rec, ended, pose, succ, ticks, lines):
-    """evaluate()'s per-instance results from the pass's per-tick records ([ticks, n] each: the
-    action taken, the queue index of an episode that ended, its final pose and success).  The
-    same under both protocols: the ending tick's record is the episode's last action, and the
-    pose is the final state's (the language protocol's: after the ending step).  lines: where
-    the reference raises, for the two messages."""
-    n, T, count = sim.n_envs, sim.config.max_timesteps, len(specs)
-    n_actions, success, end_pose, seqs = _cut_episodes(ended, pose, succ, count, rec, T)
+    """evaluate()'s per-instance results from the pass's per-tick records (device tensors
+    [ticks, n]: the action taken, the queue index of an episode that ended, its final pose and
+    success), in one craft_episode_summary call: the records stay on the device and only the
+    per-episode results come back.  The same under both protocols: the ending tick's record is
+    the episode's last action, and the pose is the final state's (the language protocol's: after
+    the ending step).  The simulator's slots are not touched.  lines: where the reference
+    raises, for the two messages."""
+    count = len(specs)
+    out = sim.episode_summary(ended, pose, succ, action_record=rec, count=count)
+    n_actions, success, pose_word, distances, seqs, flags = (
+        out[k].cpu().numpy() for k in ("length", "success", "end_pose", "distance", "actions", "flags"))
+    sim.check()                                  # an entry or a pose out of range in the records
     if (success == -2).any():
         raise RuntimeError(f"evaluate: instance {int(np.argmax(success == -2))} was never finished")
-    if (success < 0).any():
+    if flags[0] or (success < 0).any():
         raise RolloutError(f"satisfies() returned None for a finished episode ({lines[0]})")
+    end_pose = np.stack(_pose_xyd(pose_word), 1).astype(np.int32)
     goals = np.asarray([t.goal_name == "get" for t in sim.task_manager.tasks])
     is_get = goals[specs[:, 4]]
-    distances = np.where(is_get, 0, -1).astype(np.int32)
-    failed = np.nonzero(is_get & (success == 0))[0]
-    K = sim.n_kinds
-    for lo in range(0, len(failed), n):
-        idx = failed[lo:lo + n]
-        m = len(idx)
-        slots = torch.arange(m, dtype=torch.int32, device=sim.device)
-        agent = np.concatenate([end_pose[idx], np.full((m, 1), T, dtype=np.int32)], 1)
-        sim.set_state(torch.as_tensor(specs[idx]), torch.as_tensor(agent),
-                      torch.zeros((m, K), dtype=torch.int32), slots=slots)
-        plen = torch.empty(m, dtype=torch.int32, device=sim.device)
-        sim.teacher(slots=slots, path_len_out=plen)
-        distances[idx] = plen.cpu().numpy()
-    if len(failed):
-        try:                                     # the probes' own labels may raise where the
-            sim.check()                          # reference never asks: only the lengths count
-        except N.CraftError as e:
-            if e.status != N.ETEACHER:
-                raise
-    if (distances[failed] < 0).any():
+    if flags[1]:
         raise RolloutError(f"find_closest_resources found no target: len(None) ({lines[1]})")
-    eval_info = {ids[e]: {"actions": [int(a) for a in seqs[e, :n_actions[e]]], "success": int(success[e])}
-                 for e in range(count)}
+    # The reference's dict: python ints in one conversion per array, not one per action, and the
+    # collector paused meanwhile: three containers per instance, none of them garbage, and its
+    # passes over them cost several times the build itself (65,536 instances: 290 against 40 ms).
+    collecting = gc.isenabled()
+    gc.disable()
+    try:
+        eval_info = {i: {"actions": a[:k], "success": s}
+                     for i, a, k, s in zip(ids, seqs.tolist(), n_actions.tolist(), success.tolist())}
+    finally:
+        if collecting:
+            gc.enable()
     if len(eval_info) != count:
         raise ValueError("ids are not unique (imitation.py:203)")
     get_d = distances[is_get]
@@ -681,10 +678,20 @@ def _eval_summary(sim, specs, ids, rec, ended, pose, succ, ticks, lines):
                     is_get=is_get, end_pose=end_pose, ticks=ticks)
 
 
+def _summary_outs(out):
+    """What CraftSim.episode_summary returned, as the outputs of the next call over the same
+    queue entries (nothing for the first call, which allocates them)."""
+    return {k + "_out": v for k, v in out.items() if v is not None}
+
+
 class ReplayInfo(_Info):
     """replay()'s results, host arrays in the order of `specs`: success int8 (satisfies() of the
     state the episode ended in), length int32 (ticks the device ran the episode for), end_pose
-    int32 [count, 3] (x, y, dir of the final state); ticks and launches of the pass."""
+    int32 [count, 3] (x, y, dir of the final state), distances int32 (EvalInfo's: -1 where the
+    task is not a get task, 0 for a get episode that did not fail, else
+    find_closest_resources' length on the initial grid at the final pose, -1 where it finds no
+    target it can reach and -2 where it raises; None on a world the teachers refuse,
+    4 * W * H > 1000); ticks and launches of the pass."""
 
 
 def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
@@ -760,6 +767,10 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
         on_chunk(obs0[None], torch.as_tensor(shown(ep), **i32)[None], torch.zeros((1, n), **i32),
                  torch.as_tensor(shown(next_action(-1)), **i32)[None])
     rows = {k: [] for k in ("ended", "pose", "succ")}
+    # the failed get episodes' distances: one craft_episode_summary call per launch over its
+    # records, the episodes that straddle launches carried by `run`
+    with_dist = 4 * sim.width * sim.height <= 1000       # (the teachers' BFS-queue limit)
+    run, summ = torch.zeros(n, **i32), {}
     t0 = launches = 0
     while True:
         k = min(K, total - t0)
@@ -781,6 +792,9 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
         sim.rollout_stream(k, tick0=t0, actions=torch.as_tensor(acts).to(dev), obs=ring, success=succ,
                            episode_end=ended, end_pose=pose, episode_now=now)
         launches += 1
+        if with_dist:
+            summ = sim.episode_summary(ended[:k], pose[:k], succ[:k], count=count, run=run,
+                                       episode_now=now[k - 1], **_summary_outs(summ))
         for key, x in (("ended", ended), ("pose", pose), ("succ", succ)):
             rows[key].append(x[:k].cpu().numpy().copy())
         if on_chunk is not None:
@@ -800,7 +814,8 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
         e = int(bad[0])
         raise RolloutError(f"replay: the device ran episode {e} for {int(ran[e])} ticks, "
                            f"its sequence has {int(length[e])} actions")
-    return ReplayInfo(success=success, length=ran, end_pose=end_pose, ticks=t0, launches=launches)
+    return ReplayInfo(success=success, length=ran, end_pose=end_pose, ticks=t0, launches=launches,
+                      distances=summ["distance"].cpu().numpy() if with_dist else None)
 
 
 class DemonstrationInfo(_Info):

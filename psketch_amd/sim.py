@@ -659,6 +659,66 @@ class CraftSim:
                     "craft_rollout_teach_stream")
         return labels
 
+    def episode_summary(self, episode_end, end_pose, success, action_record=None, count=None, run=None,
+                        episode_now=None, length_out=None, success_out=None, end_pose_out=None,
+                        distance_out=None, actions_out=None, flags_out=None, distances=True):
+        """The per-episode results of a queue pass (include/craft.h craft_episode_summary): the
+        [ticks, N] records the four stream entry points write (episode_end, end_pose int32,
+        success int8, action_record int32 or None), rows in tick order, as results indexed by
+        queue entry 0 .. count - 1 (default: the whole queue).  No slot state is touched.
+        Returns a dict of device tensors: length int32 [count], success int8 [count] (-2: the
+        records hold no end of the entry), end_pose int32 [count] (x | y << 8 | dir << 16),
+        distance int32 [count] (as craft_rollout_distances': -1 not a get task, 0 not failed,
+        else find_closest_resources' length on the initial grid at the final pose, -1 where it
+        finds no target it can reach and -2 where it raises; None with distances=False), actions int32 [count, max_timesteps]
+        padded with -1 (None without action_record) and flags int32 [2] (a None success; a
+        failed get without a reachable target).  Outputs not passed in are allocated, success
+        pre-filled with -2 and actions with -1; ones passed in are written where the records
+        hold an end and otherwise left as they are; flags is zeroed unless passed in.
+        run (int32 [N], in/out) and episode_now (int32 [N], the episode_now row of the records'
+        last tick) carry episodes across calls over consecutive launches' records: run holds the
+        ticks each slot's current episode has already run, and an episode's action row is
+        completed by the call that sees its end."""
+        n, dev, T = self.n_envs, self.device, self.config.max_timesteps
+        if episode_end is None or episode_end.dim() != 2:
+            raise ValueError(f"episode_end must be [ticks, {n}]")
+        ticks = int(episode_end.shape[0])
+        count = int(getattr(self, "queue_count", 0) if count is None else count)
+        rows = (ticks, n)
+        args = N.craft_episode_summary_args_t()
+        keep = []
+        i32 = dict(dtype=torch.int32, device=dev)
+        if length_out is None:
+            length_out = torch.zeros(max(count, 0), **i32)
+        if success_out is None:
+            success_out = torch.full((max(count, 0),), -2, dtype=torch.int8, device=dev)
+        if end_pose_out is None:
+            end_pose_out = torch.zeros(max(count, 0), **i32)
+        if distance_out is None and distances:
+            distance_out = torch.full((max(count, 0),), -1, **i32)
+        if actions_out is None and action_record is not None:
+            actions_out = torch.full((max(count, 0), T), -1, **i32)
+        if flags_out is None:
+            flags_out = torch.zeros(2, **i32)
+        self._put_bufs(args, keep, (("episode_end", episode_end, torch.int32, rows),
+                                    ("end_pose", end_pose, torch.int32, rows),
+                                    ("success", success, torch.int8, rows),
+                                    ("action_record", action_record, torch.int32, rows),
+                                    ("run", run, torch.int32, (n,)),
+                                    ("episode_now", episode_now, torch.int32, (n,)),
+                                    ("length_out", length_out, torch.int32, (count,)),
+                                    ("success_out", success_out, torch.int8, (count,)),
+                                    ("end_pose_out", end_pose_out, torch.int32, (count,)),
+                                    ("distance_out", distance_out, torch.int32, (count,)),
+                                    ("actions_out", actions_out, torch.int32, (count, T)),
+                                    ("flags_out", flags_out, torch.int32, (2,))))
+        args.ticks = ticks
+        args.count = count
+        self._check(self._L.craft_episode_summary(self._h, ctypes.byref(args), self._stream()),
+                    "craft_episode_summary")
+        return {"length": length_out, "success": success_out, "end_pose": end_pose_out,
+                "distance": distance_out, "actions": actions_out, "flags": flags_out}
+
     @staticmethod
     def _ring_sig(*ts):
         """Storage, shape, strides, dtype and device of each output ring (a tensor resized,
