@@ -556,6 +556,57 @@ typedef struct {
 } craft_rollout_stream_args_t;
 int craft_rollout_stream(craft_sim_t* sim, const craft_rollout_stream_args_t* args, void* stream);
 
+/* Installs recorded action sequences for the installed queue, one per entry: `actions` is device
+ * int32[count][max_timesteps] (host on the CPU variant), row e = entry e's actions then -1 up to
+ * max_timesteps: the layout of craft_episode_summary's actions_out.  count must equal the queue's
+ * length.  A row is valid when it is 1..max_timesteps values in 0..5 followed only by -1, and
+ * either its last action is its only STOP or it is max_timesteps long.  A kernel checks every row
+ * and packs it into a buffer the handle owns (one byte per action, rows of max_timesteps rounded
+ * up to 4 bytes, padded with STOP); synchronous, like craft_episode_queue.  An invalid row fails
+ * the call with CRAFT_EINVAL (the message names the first such entry) and the tape installed
+ * before, if any, stays in force; so it does when the buffer cannot be allocated (CRAFT_ENOMEM).
+ * actions == NULL with count == 0 drops the tape.  craft_episode_queue drops it too (its rows
+ * mean nothing on another queue).  Moves no slot and no cursor; needs no craft_episode_begin.
+ * CRAFT_EINVAL, tested in this order: no queue installed; actions NULL with count != 0, or count
+ * != the queue's length; an invalid row. */
+int craft_episode_actions(craft_sim_t* sim, const int32_t* actions, int64_t count);
+
+/* craft_rollout_stream whose actions are the installed tape's (craft_episode_actions): n_ticks
+ * consecutive craft_step_stream ticks (label_out NULL) in one launch, exactly as
+ * craft_rollout_stream runs them, where tick k's action for slot i is read on the device.  With
+ * c the slot's queue cursor and p = max_timesteps - timer, both taken before the tick: for
+ * 0 <= p < max_timesteps the action is tape[c][p], and -1 padding reads as STOP; for any other p
+ * (which only craft_set_state can bring about, with a timer of 0 or above max_timesteps) it is
+ * STOP, and nothing latches for it.  A frozen slot's action is unused.  Every ring row, slot
+ * state, cursor, craft_stats counter and latched error is identical to those n_ticks
+ * craft_step_stream calls with those actions, and so to craft_rollout_stream given the same
+ * [n_ticks][n_envs] tensor.  Under the imitation protocol an episode then takes exactly as many
+ * ticks as its row has actions: a replay pass (Python: rollout.replay) needs no host work per
+ * tick, can be captured into a graph with no actions buffer to refresh, and runs epochs under
+ * CRAFT_QUEUE_WRAP.
+ * Two more outputs, [ring][n_envs] each and each may be NULL, both of the slot after the tick
+ * (a slot that restarted on this tick included): step_now is -1 for a frozen slot, else
+ * max_timesteps - timer, the number of actions of the current episode already taken (0 right
+ * after a restart); action_next is -1 for a frozen slot, else the action the rule above gives
+ * for the next tick.  With episode_now they are the (episode, step, action) of the state the
+ * tick's observation row shows.
+ * The action depends only on (cursor, timer), so nothing is carried between launches: a handle
+ * may mix this entry point with the four other stream entry points, craft_set_state and
+ * craft_reset between launches.  n_ticks == 0 is a no-op.
+ * CRAFT_EINVAL, tested in this order: everything craft_rollout_stream refuses, in its order;
+ * roll.actions != NULL; no tape installed for the current queue.
+ * Launch shape, ring rule, ordering, the work-unit counter shared with craft_rollout, graph
+ * capture (the graph's own counter and the memset captured with it) and "nothing allocated on
+ * the step path" as craft_rollout_stream; craft_sim_tune's tile and store policy apply.
+ * Measured against craft_rollout_stream with given actions: DESIGN.md "Recorded actions on the
+ * queue". */
+typedef struct {
+  craft_rollout_stream_args_t roll;  /* roll.actions must be NULL; action_seed is ignored */
+  int32_t* step_now;     /* [ring][n_envs] or NULL */
+  int32_t* action_next;  /* [ring][n_envs] or NULL */
+} craft_rollout_replay_args_t;
+int craft_rollout_replay(craft_sim_t* sim, const craft_rollout_replay_args_t* args, void* stream);
+
 /* craft_rollout with the DemonstrationTeacher in the same launch: n_ticks ticks, and after each
  * one DemonstrationTeacher.__call__ (teachers/demonstration.py:9-30) of every slot's new state,
  * as n_ticks craft_step_teach calls would give, with each tick's action taken per slot from

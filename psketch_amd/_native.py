@@ -154,6 +154,14 @@ class craft_rollout_stream_args_t(ctypes.Structure):
     ]
 
 
+class craft_rollout_replay_args_t(ctypes.Structure):
+    _fields_ = [
+        ("roll", craft_rollout_stream_args_t),
+        ("step_now", ctypes.c_void_p),
+        ("action_next", ctypes.c_void_p),
+    ]
+
+
 class craft_rollout_teach_args_t(ctypes.Structure):
     _fields_ = [
         ("actions", ctypes.c_void_p),
@@ -248,6 +256,8 @@ SIGNATURES = {
     "craft_step_lang_stream": (_i32, [_vp, ctypes.POINTER(craft_lang_stream_step_args_t), _vp]),
     "craft_rollout": (_i32, [_vp, _vp, _u64, _i64, _i32, _u32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "craft_rollout_stream": (_i32, [_vp, ctypes.POINTER(craft_rollout_stream_args_t), _vp]),
+    "craft_episode_actions": (_i32, [_vp, _vp, _i64]),
+    "craft_rollout_replay": (_i32, [_vp, ctypes.POINTER(craft_rollout_replay_args_t), _vp]),
     "craft_rollout_teach": (_i32, [_vp, ctypes.POINTER(craft_rollout_teach_args_t), _vp]),
     "craft_rollout_teach_stream": (_i32, [_vp, ctypes.POINTER(craft_rollout_teach_stream_args_t), _vp]),
     "craft_episode_summary": (_i32, [_vp, ctypes.POINTER(craft_episode_summary_args_t), _vp]),

@@ -31,6 +31,7 @@
 
 #include "craft_checks_episode_summary.h"
 #include "craft_checks_lang_stream.h"
+#include "craft_checks_rollout_replay.h"
 #include "craft_checks_rollout_stream.h"
 #include "craft_checks_rollout_teach_stream.h"
 #include "craft_host.h"
@@ -133,6 +134,8 @@ struct craft_sim {
   std::vector<int64_t> cursor;
   int64_t q_stride = 0;
   bool q_wrap = false, q_begun = false;
+  // craft_episode_actions: [queue.size()][max_timesteps] as given (-1 padded), empty without a tape
+  std::vector<int8_t> tape;
   std::string last_error;
 };
 
@@ -1043,6 +1046,7 @@ int craft_episode_queue(craft_sim_t* s, const int32_t* specs, int64_t count) {
   }
   s->queue.swap(q);
   s->q_begun = false;
+  s->tape.clear();                                     // a tape's rows mean nothing on another queue
   return CRAFT_OK;
 }
 
@@ -1309,6 +1313,75 @@ int craft_rollout_stream(craft_sim_t* s, const craft_rollout_stream_args_t* x, v
     t.end_pose = ring_row(x->end_pose, r, n);
     t.episode_now = ring_row(x->episode_now, r, n);
     if (const int rc = craft_step_stream(s, &t, stream)) return rc;
+  }
+  return CRAFT_OK;
+}
+
+int craft_episode_actions(craft_sim_t* s, const int32_t* actions, int64_t count) {
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_episode_actions(facts(s), actions, count, s->last_error)) return rc;
+  const int64_t T = s->cfg.max_timesteps;
+  std::vector<int8_t> tape((size_t)(count * T));
+  for (int64_t e = 0; e < count; ++e) {
+    const int32_t* row = actions + e * T;
+    int64_t len = 0;
+    while (len < T && row[len] != -1) ++len;           // the actions, then only -1
+    bool ok = len >= 1;
+    for (int64_t p = 0; p < T && ok; ++p) {
+      if (p >= len) ok = row[p] == -1;
+      else ok = row[p] >= 0 && row[p] < CRAFT_N_ACTIONS && (row[p] != CRAFT_STOP || p == len - 1);
+      tape[(size_t)(e * T + p)] = (int8_t)row[p];
+    }
+    if (ok && len < T) ok = row[len - 1] == CRAFT_STOP;   // a short row ends in its STOP
+    if (!ok) return craft_host::tape_row_invalid((uint64_t)e, s->last_error);   // the old tape stays in force
+  }
+  s->tape.swap(tape);
+  return CRAFT_OK;
+}
+
+namespace {
+// craft_rollout_replay's rule: the action of slot i as it stands, -1 for a frozen slot.
+int32_t tape_action_of(const craft_sim* s, int64_t i, int32_t* step_out) {
+  const Agent a = unpack_state(s->state[i]);
+  const int64_t T = s->cfg.max_timesteps, cur = s->cursor[(size_t)i], p = T - a.timer;
+  *step_out = a.frozen ? -1 : (int32_t)p;
+  if (a.frozen) return -1;
+  if (cur < 0 || p < 0 || p >= T) return CRAFT_STOP;
+  const int8_t x = s->tape[(size_t)(cur * T + p)];
+  return x < 0 ? CRAFT_STOP : x;
+}
+}  // namespace
+
+// craft_rollout_replay: the loop its contract names, each tick a craft_step_stream whose actions
+// are looked up on the tape from every slot's cursor and timer before the tick
+int craft_rollout_replay(craft_sim_t* s, const craft_rollout_replay_args_t* x, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_rollout_replay(facts(s), x, !s->tape.empty(), s->last_error)) return rc;
+  const craft_rollout_stream_args_t& p = x->roll;
+  const int64_t n = s->n_envs;
+  std::vector<int32_t> acts((size_t)n, 0);
+  for (int32_t k = 0; k < p.n_ticks; ++k) {
+    const int64_t r = (p.tick0 + k) % p.ring;          // tick t writes ring slot t % ring
+    int32_t step = 0;
+    for (int64_t i = 0; i < n; ++i) acts[(size_t)i] = std::max(tape_action_of(s, i, &step), 0);
+    craft_stream_step_args_t t{};
+    t.step.actions = acts.data();
+    t.step.tick = p.tick0 + k;
+    t.step.flags = p.flags;
+    t.step.obs = obs_slot(s, p.obs, r);
+    t.step.reward = ring_row(p.reward, r, n);
+    t.step.done = ring_row(p.done, r, n);
+    t.step.success = ring_row(p.success, r, n);
+    t.episode_end = ring_row(p.episode_end, r, n);
+    t.end_pose = ring_row(p.end_pose, r, n);
+    t.episode_now = ring_row(p.episode_now, r, n);
+    if (const int rc = craft_step_stream(s, &t, stream)) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+      if (!slot_valid(s, unpack_state(s->state[i]))) continue;   // the tick wrote nothing for it
+      const int32_t nx = tape_action_of(s, i, &step);
+      if (x->step_now) x->step_now[r * n + i] = step;
+      if (x->action_next) x->action_next[r * n + i] = nx;
+    }
   }
   return CRAFT_OK;
 }

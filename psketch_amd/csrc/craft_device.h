@@ -296,6 +296,13 @@ struct RolloutArgs {       // craft_rollout: n_ticks ticks in one launch
   int32_t* ep_end;
   int32_t* end_pose;
   int32_t* ep_now;
+  // craft_rollout_replay (rollout_split_kernel's TAPE instantiations), appended likewise: the
+  // packed tape (one byte per action, rows of tape_stride bytes padded with STOP) and the tick's
+  // two further outputs ([ring][n_envs] each, or null)
+  const uint8_t* tape;
+  int32_t tape_stride;
+  int32_t* step_now;
+  int32_t* act_next;
 };
 
 struct ScenarioArgs {      // craft_pool_generate

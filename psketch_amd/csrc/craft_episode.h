@@ -119,6 +119,17 @@ __device__ __forceinline__ uint32_t pose_word(const Agent& s) {
   return (uint32_t)s.x | ((uint32_t)s.y << 8) | ((uint32_t)s.dir << 16);
 }
 
+// craft_rollout_replay's action of a slot on queue entry `cur` in state s: byte p = maxT - timer of
+// the entry's tape row (one byte per action, rows of `stride` >= maxT bytes padded with STOP, as
+// craft_episode_actions packs them), STOP for a p outside the episode (a timer craft_set_state put
+// at 0 or above maxT).  A slot without an entry reads nothing; its action is unused.
+__device__ __forceinline__ int tape_action(const uint8_t* tape, const int& stride, int32_t cur, const Agent& s,
+                                           const int& maxT) {
+  const int p = maxT - s.timer;
+  if (cur < 0 || p < 0 || p >= maxT) return CRAFT_STOP;
+  return (int)tape[(int64_t)cur * stride + p];
+}
+
 // pool[scenario] (L2-resident) into the env's LDS grid row, in the lanes that restart onto another
 // scenario only: every 16-byte chunk of a batch of QB is requested before the first is used, so
 // the restart costs one more L2 round trip per batch (QB 16: the whole row at once).

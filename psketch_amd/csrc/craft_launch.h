@@ -31,6 +31,11 @@ hipError_t launch_rollout(int win, int tile, int threads, const SimView& v, cons
 // craft_rollout_stream.hip: 512 threads on rollout_stream_tile's 32- or 16-env tiles
 int rollout_stream_tile(int tile_knob, const SimView& v);
 hipError_t launch_rollout_stream(int win, int tile, const SimView& v, const RolloutArgs& a, hipStream_t st);
+// craft_rollout_replay.hip: the tape's check-and-pack kernel (rows of T int32 -> `stride` bytes),
+// and craft_rollout_stream's shapes with the tape as the action source
+hipError_t launch_tape_pack(const int32_t* actions, int64_t count, int T, int stride, uint8_t* out,
+                            unsigned long long* first_bad, hipStream_t st);
+hipError_t launch_rollout_replay(int win, int tile, const SimView& v, const RolloutArgs& a, hipStream_t st);
 hipError_t launch_rollout_teach(int win, int nw, const SimView& v, const RolloutArgs& a, hipStream_t st);
 // craft_rollout_teach_stream.hip: the same shape on the episode queue
 hipError_t launch_rollout_teach_stream(int win, int nw, const SimView& v, const RolloutArgs& a, hipStream_t st);

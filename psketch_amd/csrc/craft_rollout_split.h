@@ -43,6 +43,14 @@
 // Every restart reloads the row, so no ClearList is kept.  The tick's episode_end / end_pose /
 // episode_now go out from wave 0 beside done / success / reward; the unit's end also publishes
 // the init word and the cursor.  One unit per tile for the whole launch, never FLAT.
+//
+// TAPE (craft_rollout_replay).  QUEUE with a third action source beside GIVEN and the hashed draw:
+// the recorded sequences packed next to the queue, one byte per action in rows of a.tape_stride
+// bytes (craft_episode.h: tape_action).  The action of tick k + 1 is a function of the cursor and the timer
+// tick k leaves, and after a restart the cursor is the one whose entry was fetched an episode
+// ahead, so C(k) ends by loading it into a register (`act_nx`): the byte's L2 round trip runs
+// under the interval's barrier and the next item's buffer sync, not in front of protocol_step.
+// The same load is the tick's action_next; the unit's first action is loaded with the tile.
 #pragma once
 #include <type_traits>
 
@@ -69,10 +77,12 @@ __host__ __device__ inline int split_lds_bytes(int tile, int GS, int F, int CS, 
 // FLAT: the continuous pipeline (one unit per tile, observations on: RolloutArgs.flat);
 // otherwise work units from the queue.  Separate instantiations, so that neither path's
 // registers count against the other.
-template <int WIN, int TILE, int NT, int FMT, int WPE, bool GIVEN, bool FLAT = false, bool QUEUE = false>
+template <int WIN, int TILE, int NT, int FMT, int WPE, bool GIVEN, bool FLAT = false, bool QUEUE = false,
+          bool TAPE = false>
 __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   static_assert(!(QUEUE && FLAT), "the queue variant runs work units, one per tile");
+  static_assert(!TAPE || (QUEUE && !GIVEN), "the tape is the queue's: one row per entry");
   // scatter waves: two for 3x3 windows on 32-env tiles at 512 threads (four lanes per env, one of
   // scatter_env_part's four units each), one everywhere else (two units per lane there)
   constexpr int DW = (WIN == 3 && TILE == 32 && NT == 512) ? 2 : 1;
@@ -120,6 +130,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
   int32_t cur = -1;          // QUEUE: the slot's queue cursor (craft_episode.h)
   uint2 qe = make_uint2(0u, 0u);   // and the entry after it, fetched an episode ahead: a restart then
                                    // waits for one L2 round trip (the pool row), not for two in a row
+  int act_nx = CRAFT_STOP;   // TAPE: the next tick's action, loaded at the end of the tick before
   int sync = 0;              // how C brings its buffer up to date: 0 loaded, 1 whole copy, 2 from chg
   bool live = false;
   int64_t slot = 0;
@@ -159,7 +170,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
       }
       sync = sync ? 2 : 1;
       chg = 0;
-      const int act = GIVEN ? a.actions[(int64_t)k * n + slot] : hashed_action(v, a.seed, slot, tick);
+      const int act = TAPE ? act_nx : GIVEN ? a.actions[(int64_t)k * n + slot] : hashed_action(v, a.seed, slot, tick);
       bool restart = false;
       protocol_step(s, act, a.flags, d, counted, restart);
       if (d) succ = satisfies(v, g, iv, s, task_word);  // of the pre-step state
@@ -217,6 +228,11 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
         if (a.end_pose) a.end_pose[r * n + slot] = epose;
         if (a.ep_now) a.ep_now[r * n + slot] = s.frozen ? -1 : cur;
       }
+      if constexpr (TAPE) {                             // the next tick's action, of the slot as the tick leaves it
+        act_nx = tape_action(a.tape, a.tape_stride, cur, s, v.maxT);
+        if (a.step_now) a.step_now[r * n + slot] = s.frozen ? -1 : v.maxT - s.timer;
+        if (a.act_next) a.act_next[r * n + slot] = s.frozen ? -1 : act_nx;
+      }
     } else if (lds_out && tid < TILE) {
       s_out[(p & 3) * TILE + tid] = 0u;
     }
@@ -272,6 +288,7 @@ __global__ __launch_bounds__(NT, WPE) void rollout_split_kernel(SimView v, Rollo
         latch_error(v.err, CRAFT_EINVAL, slot);
         live = false;
       }
+      if constexpr (TAPE) act_nx = tape_action(a.tape, a.tape_stride, cur, s, v.maxT);
     }
     chg = 0;
     clr.clear();

@@ -4,7 +4,8 @@
 // language trainers' tick), craft_tick_stream.hip (the episode queue and its tick),
 // craft_tick_teach.hip (the tick fused with the teacher), craft_rollout_w3/w5/w7.hip (multi-tick),
 // craft_rollout_teach.hip (multi-tick with labels), craft_rollout_stream.hip (multi-tick on the
-// episode queue), craft_rollout_teach_stream.hip (both), craft_teacher.hip, craft_scenarios.hip (pool generation).  Their launchers:
+// episode queue), craft_rollout_replay.hip (the same with the actions read from the installed
+// tape, and the tape's pack kernel), craft_rollout_teach_stream.hip (both), craft_teacher.hip, craft_scenarios.hip (pool generation).  Their launchers:
 // craft_launch.h.
 #include <algorithm>
 #include <cstdlib>
@@ -16,6 +17,7 @@
 #include "craft_device.h"
 #include "craft_checks_episode_summary.h"
 #include "craft_checks_lang_stream.h"
+#include "craft_checks_rollout_replay.h"
 #include "craft_checks_rollout_stream.h"
 #include "craft_checks_rollout_teach_stream.h"
 #include "craft_host.h"
@@ -175,6 +177,8 @@ struct craft_sim {
   unsigned long long* d_qbad = nullptr;   // the lowest invalid index of a queue being installed
   uint32_t q_step = 0, q_wrap = 0;  // craft_episode_begin's stride (reduced, craft_episode.h) and WRAP
   bool q_begun = false;             // craft_episode_begin since the queue was installed
+  uint8_t* d_tape = nullptr;        // craft_episode_actions: [q_count][tape_stride] bytes, or null (no tape)
+  int32_t tape_stride = 0;          // max_timesteps rounded up to 4; the rest of a row is STOP
   std::string last_error;
 };
 
@@ -818,6 +822,7 @@ int craft_sim_destroy(craft_sim_t* s) {
   (void)hipFree(s->d_ttab4);
   (void)hipFree(s->d_ttcells);
   (void)hipFree(s->d_queue);
+  (void)hipFree(s->d_tape);
   (void)hipFree(s->d_cursor);
   (void)hipFree(s->d_qreset);
   (void)hipFree(s->d_qbad);
@@ -1056,6 +1061,8 @@ int craft_episode_queue(craft_sim_t* s, const int32_t* specs, int64_t count) {
   (void)hipFree(s->d_queue);
   s->d_queue = q;
   s->q_count = count;
+  (void)hipFree(s->d_tape);                  // a tape's rows mean nothing on another queue
+  s->d_tape = nullptr;
   s->q_begun = false;                        // cursors of the old queue mean nothing on this one
   return CRAFT_OK;
 }
@@ -1175,6 +1182,57 @@ int craft_rollout_stream(craft_sim_t* s, const craft_rollout_stream_args_t* x, v
   view.obs_policy = s->rollout_obs_policy;
   return launch_tile_units(s, tile, a, stream, "craft_rollout_stream launch", [&](hipStream_t st) {
     return craft::launch_rollout_stream(s->cfg.window_width, tile, view, a, st);
+  });
+}
+
+int craft_episode_actions(craft_sim_t* s, const int32_t* actions, int64_t count) {
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_episode_actions(facts(s), actions, count, s->last_error)) return rc;
+  HIP_TRY(s, hipSetDevice(s->device));
+  uint8_t* tape = nullptr;
+  const int T = s->cfg.max_timesteps, stride = (T + 3) & ~3;
+  if (actions) {
+    if (hipMalloc(&tape, (size_t)count * (size_t)stride) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(s, CRAFT_ENOMEM, "craft_episode_actions: out of device memory");
+    }
+    unsigned long long bad = ~0ull;                // (d_qbad: the queue's install allocated it)
+    hipError_t e = hipMemcpy(s->d_qbad, &bad, sizeof(bad), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = craft::launch_tape_pack(actions, count, T, stride, tape, s->d_qbad, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(&bad, s->d_qbad, sizeof(bad), hipMemcpyDeviceToHost);   // (waits for the kernel)
+    if (e != hipSuccess) {
+      (void)hipFree(tape);
+      return hip_fail(s, e, "craft_episode_actions");
+    }
+    if (bad != ~0ull) {
+      (void)hipFree(tape);                         // the tape installed before stays in force
+      return craft_host::tape_row_invalid(bad, s->last_error);
+    }
+  }
+  // launches that read the old tape may still be running on some stream: they finish first
+  HIP_TRY(s, hipDeviceSynchronize());
+  (void)hipFree(s->d_tape);
+  s->d_tape = tape;
+  s->tape_stride = stride;
+  return CRAFT_OK;
+}
+
+int craft_rollout_replay(craft_sim_t* s, const craft_rollout_replay_args_t* x, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  int rc = craft_host::check_rollout_replay(facts(s), x, s->d_tape != nullptr, s->last_error);
+  if (rc != CRAFT_OK) return rc;
+  if (x->roll.n_ticks == 0) return CRAFT_OK;
+  craft::RolloutArgs a = rollout_args(x->roll);
+  queue_args(s, x->roll, a);
+  a.tape = s->d_tape;
+  a.tape_stride = s->tape_stride;
+  a.step_now = x->step_now;
+  a.act_next = x->action_next;
+  const int tile = craft::rollout_stream_tile(s->k.tile_knob, s->view);
+  SimView view = s->view;
+  view.obs_policy = s->rollout_obs_policy;
+  return launch_tile_units(s, tile, a, stream, "craft_rollout_replay launch", [&](hipStream_t st) {
+    return craft::launch_rollout_replay(s->cfg.window_width, tile, view, a, st);
   });
 }
 

@@ -516,7 +516,7 @@ def _specs_array(specs):
     return specs
 
 
-def _begin_pass(sim, specs, obs=None):
+def _begin_pass(sim, specs, obs=None, wrap=False):
     """Starts one pass over `specs` (a _specs_array): installs them as the episode queue and
     puts slot i on row i, to take rows i + n, i + 2n, ... after it.  Every slot needs a first
     entry, so a split shorter than n_envs is padded with copies of its first row, whose episodes
@@ -524,7 +524,7 @@ def _begin_pass(sim, specs, obs=None):
     n, count = sim.n_envs, len(specs)
     queue = specs if count >= n else np.concatenate([specs, np.repeat(specs[:1], n - count, 0)])
     sim.set_episode_queue(torch.as_tensor(queue))
-    sim.begin_episodes(first=0, stride=n, wrap=False, obs=obs)
+    sim.begin_episodes(first=0, stride=n, wrap=wrap, obs=obs)
     return queue, count, len(queue)
 
 
@@ -694,17 +694,20 @@ class ReplayInfo(_Info):
     4 * W * H > 1000); ticks and launches of the pass."""
 
 
-def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
+def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None, epochs=1):
     """One pass over `specs` driven by recorded actions (a dataset's demonstrations, or the
-    `actions` of an EvalInfo), K ticks per launch on the episode queue (craft_rollout_stream):
+    `actions` of an EvalInfo), K ticks per launch on the episode queue (craft_rollout_replay):
     the (state, action) pairs behaviour cloning trains on, without a launch per tick.
 
     specs: as evaluate()'s.  action_seqs[e]: episode e's actions, each 0..5, at most
       max_timesteps of them, ending in its only STOP or max_timesteps long; ValueError names the
-      first episode that is neither.  Under the imitation protocol such an episode takes exactly
+      first episode that is neither.  Or all of them as one int array or tensor [count, <=
+      max_timesteps], each row padded with -1 (DemonstrationInfo.action_seqs,
+      EvalInfo.action_seqs).  Under the imitation protocol such an episode takes exactly
       len(action_seqs[e]) ticks, so slot i's action stream is the sequences of episodes i,
-      i + n, i + 2n, ... one after the other, and each launch's [K, n] action tensor is laid
-      out on the host.
+      i + n, i + 2n, ... one after the other.  The sequences are installed once beside the queue
+      (craft_episode_actions) and every launch reads its own actions on the device: the host
+      lays out no action tensor and copies nothing back until the pass is over.
     on_chunk(obs, episode, step, action): called with [K, n, ...] device tensors, first with
       the K = 1 chunk of begin_episodes' observations, then once per launch (the tensors are
       overwritten by the next launch).  obs[k, i] is slot i's state after that tick, in the
@@ -712,108 +715,132 @@ def replay(sim, specs, action_seqs, ticks_per_launch=32, on_chunk=None):
       slot; step (int32) how many of that episode's actions were already taken; action (int32)
       the recorded action taken next from that state, action_seqs[episode][step], or -1 for an
       idle slot.  Over the pass the rows with action >= 0 are the (state, action) pairs of
-      every sequence, each exactly once.
-    Returns a ReplayInfo.  RolloutError if the device ran an episode for another number of ticks
-    than its sequence has, or latched an error."""
+      every sequence, each exactly once per epoch.
+    epochs: with epochs > 1 the pass runs that many times over under CRAFT_QUEUE_WRAP, in one
+      stream of launches; len(specs) must then be a multiple of n_envs (ValueError), so that a
+      slot's stream of episodes repeats as it is.
+    Returns a ReplayInfo (of the last end of every episode).  RolloutError if the device ran an
+    episode for another number of ticks than its sequence has, or latched an error."""
     n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
-    K = int(ticks_per_launch)
+    K, epochs = int(ticks_per_launch), int(epochs)
     if K < 1:
         raise ValueError("ticks_per_launch must be >= 1")
+    if epochs < 1:
+        raise ValueError("epochs must be >= 1")
     specs = _specs_array(specs)
     if len(action_seqs) != len(specs):
         raise ValueError(f"{len(action_seqs)} action sequences for {len(specs)} specs")
-    seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in action_seqs]
-    for e, s in enumerate(seqs):
-        if len(s) > T:
-            raise ValueError(f"episode {e}: {len(s)} actions, max_timesteps is {T}")
-        if ((s < 0) | (s >= N.N_ACTIONS)).any():
+    if epochs > 1 and len(specs) % n:
+        raise ValueError(f"epochs > 1 needs len(specs) to be a multiple of n_envs ({len(specs)} % {n})")
+    count = len(action_seqs)
+    # every sequence checked in one pass over their concatenation (the first bad episode is named)
+    if isinstance(action_seqs, (np.ndarray, torch.Tensor)) and action_seqs.ndim == 2:
+        rows = np.asarray(torch.as_tensor(action_seqs).cpu())
+        some = rows != -1                                 # a row runs up to its last value that is no padding
+        lens = np.where(some.any(1), rows.shape[1] - np.argmax(some[:, ::-1], 1), 0).astype(np.int64)
+        flat = rows[np.arange(rows.shape[1])[None] < lens[:, None]].astype(np.int64)
+    else:
+        try:                                              # (lists or 1-d arrays: no pass of our own over them)
+            lens = np.fromiter(map(len, action_seqs), dtype=np.int64, count=count)
+            flat = np.concatenate(action_seqs) if lens.sum() else np.zeros(0)
+        except (TypeError, ValueError):                   # a 0-d or 2-d entry: flattened, as ever
+            lens = np.fromiter((np.size(s) for s in action_seqs), dtype=np.int64, count=count)
+            flat = np.concatenate([np.reshape(s, -1) for s in action_seqs]) if lens.sum() else np.zeros(0)
+        flat = flat.astype(np.int64)
+    ends = np.cumsum(lens)
+
+    def owners(at):                                       # the episodes of positions `at` of flat
+        return np.searchsorted(ends, at, side="right")
+    outside = np.zeros(count, dtype=bool)
+    outside[owners(np.nonzero((flat < 0) | (flat >= N.N_ACTIONS))[0])] = True
+    first_stop = np.full(count, T + 1, dtype=np.int64)
+    stops = np.nonzero(flat == N.STOP)[0]                 # (in episode order: the first of each is its first)
+    who, at = np.unique(owners(stops), return_index=True)
+    first_stop[who] = stops[at] - (ends - lens)[who]
+    stopped = first_stop <= T
+    early = stopped & (first_stop != lens - 1)
+    bad = (lens > T) | outside | early | (~stopped & (lens != T))
+    if bad.any():
+        e = int(np.argmax(bad))
+        if lens[e] > T:
+            raise ValueError(f"episode {e}: {int(lens[e])} actions, max_timesteps is {T}")
+        if outside[e]:
             raise ValueError(f"episode {e}: an action outside 0..{N.N_ACTIONS - 1}")
-        stops = np.nonzero(s == N.STOP)[0]
-        if len(stops) and stops[0] != len(s) - 1:
-            raise ValueError(f"episode {e}: STOP at step {int(stops[0])}, before its end")
-        if not len(stops) and len(s) != T:
-            raise ValueError(f"episode {e}: {len(s)} actions without a STOP (max_timesteps is {T})")
+        if early[e]:
+            raise ValueError(f"episode {e}: STOP at step {int(first_stop[e])}, before its end")
+        raise ValueError(f"episode {e}: {int(lens[e])} actions without a STOP (max_timesteps is {T})")
+    wrap = epochs > 1
     obs0 = sim.empty_obs()
-    _, count, Q = _begin_pass(sim, specs, obs0)
-    seqs = seqs + [np.asarray([N.STOP], dtype=np.int64)] * (Q - count)   # the padding STOPs at once
-    length = np.asarray([len(s) for s in seqs], dtype=np.int64)
-    off = np.concatenate([[0], np.cumsum(length)])[:-1]
-    flat = np.concatenate(seqs).astype(np.int32)
-    # ticks of the pass: the longest slot stream
+    _, count, Q = _begin_pass(sim, specs, obs0, wrap=wrap)
+    # the tape: one -1 padded row per queue entry, the padding entries STOP at once
+    length = np.ones(Q, dtype=np.int64)
+    length[:count] = lens
+    tape = np.full((Q, T), -1, dtype=np.int32)
+    tape[:, 0] = N.STOP
+    tape[:count][np.arange(T)[None] < lens[:, None]] = flat
+    sim.set_episode_actions(torch.as_tensor(tape))
+    # ticks of the pass: the longest slot stream (every slot's, under wrap, once per epoch)
     per_slot = np.zeros(n, dtype=np.int64)
     np.add.at(per_slot, np.arange(Q) % n, length)
-    total = int(per_slot.max())
+    total = int(per_slot.max()) * epochs
+    limit = torch.as_tensor(per_slot * epochs, device=dev)
 
     i32 = dict(dtype=torch.int32, device=dev)
-    ring = torch.empty((K, n, sim.n_features), dtype=sim.obs_dtype, device=dev)
+    ring = torch.empty((K, n, sim.n_features), dtype=sim.obs_dtype, device=dev) if on_chunk is not None else None
     ended = torch.empty((K, n), **i32)
     pose = torch.empty((K, n), **i32)
     now = torch.empty((K, n), **i32)
+    step = torch.empty((K, n), **i32) if on_chunk is not None else None
+    nxt = torch.empty((K, n), **i32) if on_chunk is not None else None
     succ = torch.empty((K, n), dtype=torch.int8, device=dev)
 
-    ep = np.arange(n, dtype=np.int64)                    # the episode each slot is on, -1: none left
-    st = np.zeros(n, dtype=np.int64)                     # actions of it already taken
-
-    def next_action(idle):
-        a = np.full(n, idle, dtype=np.int32)
-        on = ep >= 0
-        a[on] = flat[off[ep[on]] + st[on]]
-        return a
-
-    def shown(a):                                        # a padding episode's rows are nobody's pairs
-        return np.where(ep < count, a, -1).astype(np.int32)
+    def shown(episode, action):                          # a padding episode's rows are nobody's pairs
+        pad = episode >= count
+        return (torch.where(pad, -1, episode).to(torch.int32),
+                torch.where(pad, -1, action).to(torch.int32))
 
     if on_chunk is not None:
-        on_chunk(obs0[None], torch.as_tensor(shown(ep), **i32)[None], torch.zeros((1, n), **i32),
-                 torch.as_tensor(shown(next_action(-1)), **i32)[None])
-    rows = {k: [] for k in ("ended", "pose", "succ")}
-    # the failed get episodes' distances: one craft_episode_summary call per launch over its
-    # records, the episodes that straddle launches carried by `run`
+        first = torch.arange(n, **i32)
+        ep0, ac0 = shown(first, torch.as_tensor(tape[:n, 0].copy(), **i32))
+        on_chunk(obs0[None], ep0[None], torch.zeros((1, n), **i32), ac0[None])
+    # length, success, end_pose and the failed get episodes' distances: one
+    # craft_episode_summary call per launch over its records, the episodes that straddle
+    # launches carried by `run`; everything stays on the device until the pass is over
     with_dist = 4 * sim.width * sim.height <= 1000       # (the teachers' BFS-queue limit)
     run, summ = torch.zeros(n, **i32), {}
     t0 = launches = 0
-    while True:
+    while t0 < total:
         k = min(K, total - t0)
-        if k <= 0:
-            raise RolloutError(f"replay: slots still running after {t0} ticks")
-        acts = np.zeros((k, n), dtype=np.int32)
-        c_st = np.empty((k, n), dtype=np.int32)
-        c_act = np.empty((k, n), dtype=np.int32)
-        for j in range(k):
-            acts[j] = next_action(0)                     # (an idle slot's action is ignored)
-            on = ep >= 0
-            st[on] += 1
-            over = on & (st == length[np.maximum(ep, 0)])
-            nxt = ep[over] + n
-            ep[over] = np.where(nxt < Q, nxt, -1)
-            st[over] = 0
-            c_st[j], c_act[j] = st, shown(next_action(-1))
         # tick0 is a multiple of K, so tick t0 + j writes ring slot j
-        sim.rollout_stream(k, tick0=t0, actions=torch.as_tensor(acts).to(dev), obs=ring, success=succ,
-                           episode_end=ended, end_pose=pose, episode_now=now)
+        sim.rollout_replay(k, tick0=t0, obs=ring, success=succ, episode_end=ended, end_pose=pose,
+                           episode_now=now, step_now=step, action_next=nxt)
         launches += 1
-        if with_dist:
-            summ = sim.episode_summary(ended[:k], pose[:k], succ[:k], count=count, run=run,
-                                       episode_now=now[k - 1], **_summary_outs(summ))
-        for key, x in (("ended", ended), ("pose", pose), ("succ", succ)):
-            rows[key].append(x[:k].cpu().numpy().copy())
+        summ = sim.episode_summary(ended[:k], pose[:k], succ[:k], count=count, run=run,
+                                   episode_now=now[k - 1], distances=with_dist, **_summary_outs(summ))
         if on_chunk is not None:
-            episode = torch.where(now[:k] >= count, -1, now[:k]).to(torch.int32)
-            on_chunk(ring[:k], episode, torch.as_tensor(c_st, **i32), torch.as_tensor(c_act, **i32))
+            episode, action = shown(now[:k], nxt[:k])
+            if wrap:                                     # a slot through its epochs early shows as idle
+                over = torch.arange(t0 + 1, t0 + k + 1, device=dev)[:, None] >= limit[None]
+                episode, action = torch.where(over, -1, episode), torch.where(over, -1, action)
+            # an idle slot: episode -1, step 0, action -1, as a padding episode's rows
+            on_chunk(ring[:k], episode, torch.where(episode < 0, 0, step[:k]).to(torch.int32), action)
         t0 += k
-        if (now[k - 1].cpu().numpy() < 0).all():
-            break
+        last = now[k - 1]
+    # the pass's one read-back
+    ran, success, pose_word, running = (x.cpu().numpy() for x in
+                                        (summ["length"], summ["success"], summ["end_pose"], last >= 0))
     try:
         sim.check()                                      # an error latched during the pass
     except N.CraftError as e:
         raise RolloutError(f"replay: {e}") from e
-    ran, success, end_pose, _ = _cut_episodes(*(np.concatenate(rows[k]) for k in
-                                                ("ended", "pose", "succ")), count)
+    if not wrap and running.any():
+        raise RolloutError(f"replay: slots still running after {t0} ticks")
     bad = np.nonzero(ran != length[:count])[0]
     if len(bad):
         e = int(bad[0])
         raise RolloutError(f"replay: the device ran episode {e} for {int(ran[e])} ticks, "
                            f"its sequence has {int(length[e])} actions")
+    end_pose = np.stack(_pose_xyd(pose_word), 1).astype(np.int32)
     return ReplayInfo(success=success, length=ran, end_pose=end_pose, ticks=t0, launches=launches,
                       distances=summ["distance"].cpu().numpy() if with_dist else None)
 

@@ -305,12 +305,13 @@ class CraftSim:
                                   ("episode_now", episode_now, torch.int32, shape)))
 
     def _rollout_fields(self, st, keep, n_ticks, seed, tick0, flags, actions, obs, reward, done, success,
-                        more=(), queue=None):
+                        more=(), queue=None, more_on=None):
         """The ring outputs, the actions and the five launch words of a struct-taking K-tick
         rollout (rollout_stream, rollout_teach, rollout_teach_stream): obs [R, N, F] and reward,
         done, success [R, N], then `more` ((field, tensor) rows: the entry's further int32 [R, N]
-        outputs), then the queue outputs (queue: the struct that holds them, episode_end,
-        end_pose, episode_now).  R is that of the first ring given."""
+        outputs, fields of `more_on` where that is not the struct itself), then the queue outputs
+        (queue: the struct that holds them, episode_end, end_pose, episode_now).  R is that of
+        the first ring given."""
         n = self.n_envs
         named = [("obs", obs), ("reward", reward), ("done", done), ("success", success), *more]
         if queue is not None:
@@ -320,8 +321,9 @@ class CraftSim:
         self._put_bufs(st, keep, [("obs", obs, self.obs_dtype, (ring, n, self.n_features)),
                                   ("reward", reward, torch.float32, shape),
                                   ("done", done, torch.uint8, shape),
-                                  ("success", success, torch.int8, shape),
-                                  *[(field, t, torch.int32, shape) for field, t in more]])
+                                  ("success", success, torch.int8, shape)])
+        self._put_bufs(st if more_on is None else more_on, keep,
+                       [(field, t, torch.int32, shape) for field, t in more])
         if queue is not None:
             self._queue_outs(queue[0], keep, shape, *queue[1:])
         if actions is not None:
@@ -579,6 +581,44 @@ class CraftSim:
                              success, queue=(args, episode_end, end_pose, episode_now))
         self._check(self._L.craft_rollout_stream(self._h, ctypes.byref(args), self._stream()),
                     "craft_rollout_stream")
+        return obs
+
+    def set_episode_actions(self, actions):
+        """Install the recorded action sequences of the installed queue (craft_episode_actions):
+        a device or host int tensor [count, max_timesteps], row e = entry e's actions then -1, one
+        row per queue entry (the layout of episode_summary's and rollout.demonstrations' action
+        arrays).  Every row is checked on the device; an invalid one raises (EINVAL, naming the
+        first) and the tape installed before stays.  None drops the tape; set_episode_queue
+        drops it too.  Synchronous."""
+        if actions is None:
+            self._check(self._L.craft_episode_actions(self._h, None, 0), "craft_episode_actions")
+            return
+        a = torch.as_tensor(actions)
+        T = self.config.max_timesteps
+        if a.dim() != 2 or a.shape[1] != T:
+            raise ValueError(f"actions must be [count, {T}], got {tuple(a.shape)}")
+        a = a.to(device=self.device, dtype=torch.int32).contiguous()
+        self._check(self._L.craft_episode_actions(self._h, _ptr(a), int(a.shape[0])),
+                    "craft_episode_actions")
+
+    def rollout_replay(self, n_ticks, tick0=0, obs=None, reward=None, done=None, success=None,
+                       episode_end=None, end_pose=None, episode_now=None, step_now=None,
+                       action_next=None):
+        """rollout_stream whose actions are the installed tape's (include/craft.h
+        craft_rollout_replay): every slot's action is read on the device from its queue entry's
+        recorded sequence at the step its timer names, so the launch takes no actions tensor.
+        Outputs as rollout_stream's, and two more int32 [R, N] rings of the slot after the tick:
+        step_now (actions of its current episode already taken, -1 for a frozen slot) and
+        action_next (the action it takes next, -1 for a frozen slot)."""
+        if n_ticks < 0:
+            raise ValueError("n_ticks must be >= 0")
+        args = N.craft_rollout_replay_args_t()
+        keep = []
+        self._rollout_fields(args.roll, keep, n_ticks, 0, tick0, N.STEP_AUTORESET, None, obs, reward, done,
+                             success, more=(("step_now", step_now), ("action_next", action_next)),
+                             queue=(args.roll, episode_end, end_pose, episode_now), more_on=args)
+        self._check(self._L.craft_rollout_replay(self._h, ctypes.byref(args), self._stream()),
+                    "craft_rollout_replay")
         return obs
 
     def rollout_teach(self, n_ticks, seed=0, tick0=0, actions=None, autoreset=True, obs=None,
