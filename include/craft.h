@@ -156,7 +156,14 @@ int craft_sim_info(const craft_sim_t* sim, int64_t* n_envs, int32_t* pool_capaci
  * every kernel stores write-through (sc1; the measured best for craft_rollout and for a
  * tick that rewrites one buffer) except craft_rollout_teach, which stores nontemporal (its
  * teacher-table gathers keep their L2 lines: 7-15 % faster at 65,536 envs).
- * Note: craft_sim_tune(.., 0, 0, 0) selects write-back. */
+ * Note: craft_sim_tune(.., 0, 0, 0) selects write-back.
+ * CRAFT_EINVAL, and the handle keeps its knobs: a value outside the ranges above, or a tile whose
+ * one-tick working set does not fit a workgroup's 160 KiB of LDS, that is
+ *   tile_envs * (((WIDTH*HEIGHT + 15) & ~15) + n_features + 44) + 688 > 163840
+ * (64-env tiles at 7x7 windows, from 23 kinds on the largest worlds; a 32-env tile always fits).  Both libraries refuse
+ * it, so no tick ever launches a tile that cannot be carved; where craft_step_teach's one-tile
+ * kernel would pick 64-env tiles of its own that do not fit, it runs 32-env tiles
+ * (craft_sim_step_shape reports them). */
 int craft_sim_tune(craft_sim_t* sim, int32_t tile_envs, int32_t max_resident_per_cu,
                    int32_t obs_store);
 

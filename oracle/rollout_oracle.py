@@ -98,7 +98,7 @@ def fake_policy(W, bias):
 
 
 def teach_rollout(oracle, envs, gids, n_ticks, seed=0, tick0=0, actions=None, autoreset=True,
-                  label_in=None, label_src=None, want_obs=False):
+                  label_in=None, label_src=None, want_obs=False, watch=None):
     """craft_rollout_teach restated over the C oracle, one env at a time: each tick the action of
     env i is its current label when label_src[i] (make_data.get_reference_actions,
     make_data.py:146-152; behaviour cloning, trainers/imitation.py:56-57), else actions[k][i] or
@@ -106,7 +106,9 @@ def teach_rollout(oracle, envs, gids, n_ticks, seed=0, tick0=0, actions=None, au
     DemonstrationTeacher of the new state (-1 for a frozen env, -2 where the reference raises).
     envs: oracle envs (modified in place).  Returns per-tick arrays [n_ticks, n]: labels,
     action_record (-1 for an env already done), done, success; with want_obs also obs
-    [n_ticks, n, F] (float32, features() of each env's state after the tick)."""
+    [n_ticks, n, F] (float32, features() of each env's state after the tick).  watch (with
+    want_obs): an object told every tick (tick(envs before, actions, envs after, done, autoreset,
+    obs)) and its labels (query(envs, labels))."""
     import oracle as O
     n = len(envs)
     gids = np.asarray(gids, dtype=np.int64)
@@ -126,6 +128,7 @@ def teach_rollout(oracle, envs, gids, n_ticks, seed=0, tick0=0, actions=None, au
             else:
                 a[i] = O.hash_action(seed, int(gids[i]), t)
         frozen = envs["frozen"].copy()
+        pre = envs.copy() if watch is not None else None
         rows = []
         for i in range(n):
             rc, ob, _, d, s = oracle.batch_tick(envs[i:i + 1], int(gids[i]), a[i:i + 1], seed, t, autoreset,
@@ -146,6 +149,9 @@ def teach_rollout(oracle, envs, gids, n_ticks, seed=0, tick0=0, actions=None, au
                 rc, lab = oracle.teacher(envs[i:i + 1], int(envs["task"][i]))
                 cur[i] = -2 if rc else lab
         out["labels"][k] = cur
+        if watch is not None:
+            watch.tick(pre, a, envs, out["done"][k], autoreset, obs[-1])
+            watch.query(envs, cur)
     if want_obs:
         out["obs"] = np.stack(obs)
     return out

@@ -77,11 +77,26 @@ struct Knobs {
   int obs_fmt = CRAFT_OBS_F32;
 };
 
-inline int set_tune(Knobs& k, int win, int32_t tile_envs, int32_t max_resident_per_cu, int32_t obs_store,
-                    std::string& msg) {
+// Whether a one-tick tile of `tile` envs fits a workgroup's 160 KiB of LDS (include/craft.h,
+// craft_sim_tune): per env a grid row of ((W*H + 15) & ~15) + 4 bytes, the staged observation row
+// (n_features bytes), 36 bytes of inventory and 4 of agent state; 688 bytes for the task and
+// recipe tables, the subtask bytes of the teacher's tick, the control words and their 16-byte
+// padding.  Never less than what craft_device.h lds_layout carves, so a tile that passes launches
+// (craft_sim.hip craft_debug_tile_fits_drift checks that over the ABI's ranges).
+// A 32-env tile fits every configuration the ABI admits (at most 111,824 bytes).
+inline int64_t tile_lds_bound(int tile, int cells, int n_features) {
+  return (int64_t)tile * (((cells + 15) & ~15) + 4 + n_features + 40) + 688;
+}
+inline bool tile_fits(int tile, int cells, int n_features) { return tile_lds_bound(tile, cells, n_features) <= 163840; }
+
+inline int set_tune(Knobs& k, int win, int cells, int n_features, int32_t tile_envs, int32_t max_resident_per_cu,
+                    int32_t obs_store, std::string& msg) {
   const int tile = tile_envs == 0 ? default_tile(win) : tile_envs;
   if (tile != 16 && tile != 32 && tile != 64)
     return refuse(msg, CRAFT_EINVAL, "craft_sim_tune: tile_envs must be 16, 32 or 64");
+  if (!tile_fits(tile, cells, n_features))
+    return refuse(msg, CRAFT_EINVAL,
+                  "craft_sim_tune: a tile of tile_envs envs does not fit a workgroup's 160 KiB of LDS with this window and kind count");
   if (max_resident_per_cu != 0 && (max_resident_per_cu < 3 || max_resident_per_cu > 32))
     return refuse(msg, CRAFT_EINVAL, "craft_sim_tune: max_resident_per_cu must be 0 or 3..32");
   if (obs_store < 0 || obs_store > 2)

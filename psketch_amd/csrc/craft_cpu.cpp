@@ -722,7 +722,7 @@ int craft_sim_info(const craft_sim_t* s, int64_t* n_envs, int32_t* pool_capacity
 // shape queries; they change nothing here (there are no workgroups).
 int craft_sim_tune(craft_sim_t* s, int32_t tile_envs, int32_t max_resident_per_cu, int32_t obs_store) {
   if (!s) return CRAFT_EINVAL;
-  return craft_host::set_tune(s->k, s->win, tile_envs, max_resident_per_cu, obs_store, s->last_error);
+  return craft_host::set_tune(s->k, s->win, s->C, s->F, tile_envs, max_resident_per_cu, obs_store, s->last_error);
 }
 
 int craft_sim_tune_rollout(craft_sim_t* s, int32_t chunk_ticks, int32_t threads) {

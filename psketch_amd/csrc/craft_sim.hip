@@ -246,9 +246,12 @@ void rollout_shape(const craft_sim* s, int* tile, int* threads, int* split) {
 }
 
 // The one-tile teacher kernel's envs per tile: 64 for 3x3 windows; the handle's tile (default 32)
-// for wider ones, whose 64-env observation rows (69 KB at 5x5) leave one workgroup per CU.
+// for wider ones, whose 64-env observation rows (69 KB at 5x5) leave one workgroup per CU; 32 also
+// where 64 envs do not fit a workgroup's LDS (craft_host::tile_fits: 7x7 windows, from 23 kinds on the
+// largest worlds).
 int teach_tile(const craft_sim* s) {
-  return s->cfg.window_width == 3 || s->k.tile != 32 ? craft::kMaxTileEnvs : 32;
+  const int t = s->cfg.window_width == 3 || s->k.tile != 32 ? craft::kMaxTileEnvs : 32;
+  return craft_host::tile_fits(t, s->view.C, s->view.F) ? t : 32;
 }
 
 // Teacher lanes per env of the one-tile kernel (craft_sim_tune_teach): quads, or pairs on the
@@ -751,8 +754,8 @@ int craft_sim_create(const craft_config_t* cfg, int device, int64_t n_envs, int6
 
 int craft_sim_tune(craft_sim_t* s, int32_t tile_envs, int32_t max_resident_per_cu, int32_t obs_store) {
   if (!s) return CRAFT_EINVAL;
-  if (const int rc = craft_host::set_tune(s->k, s->cfg.window_width, tile_envs, max_resident_per_cu, obs_store,
-                                          s->last_error))
+  if (const int rc = craft_host::set_tune(s->k, s->cfg.window_width, s->view.C, s->view.F, tile_envs,
+                                          max_resident_per_cu, obs_store, s->last_error))
     return rc;
   s->view.obs_policy = obs_store;
   s->rollout_obs_policy = obs_store;
@@ -763,6 +766,30 @@ int craft_sim_tune(craft_sim_t* s, int32_t tile_envs, int32_t max_resident_per_c
 int craft_sim_tune_teach(craft_sim_t* s, int32_t kernel, int32_t lanes, int32_t table) {
   if (!s) return CRAFT_EINVAL;
   return craft_host::set_tune_teach(s->k, kernel, lanes, table, s->last_error);
+}
+
+// Test hook, not part of include/craft.h (host code only, no device needed): craft_host::tile_fits
+// restates the size of the one-tick carve by hand, so that both libraries can refuse a tile;
+// this counts the (tile, WIDTH*HEIGHT, window, kinds) of the ABI's ranges for which it says "fits"
+// while lds_layout plus the teacher tick's subtask bytes (tick_plan) exceed a workgroup's LDS, or
+// for which the carve is larger than the bound tile_fits compares.  Both counts must stay 0
+// (tests/test_cookbook_limits.py); *checked = the combinations looked at.
+int craft_debug_tile_fits_drift(int64_t* checked) {
+  int bad = 0;
+  int64_t n = 0;
+  const size_t sub = ((size_t)CRAFT_MAX_TASKS * CRAFT_MAX_SUBTASKS + 15) & ~size_t(15);
+  for (int tile = craft::kMinTileEnvs; tile <= craft::kMaxTileEnvs; tile *= 2)
+    for (int cells = 9; cells <= CRAFT_MAX_CELLS; ++cells)
+      for (int win = 3; win <= 7; win += 2)
+        for (int K = 2; K <= CRAFT_MAX_KINDS; ++K, ++n) {
+          const int F = 2 * win * win * K + K + 5, GS = ((cells + 15) & ~15) + 4;
+          const size_t carve = (size_t)craft::lds_layout(tile, GS, F).bytes + sub;
+          if ((int64_t)carve > craft_host::tile_lds_bound(tile, cells, F) ||
+              (craft_host::tile_fits(tile, cells, F) && carve > 163840))
+            ++bad;
+        }
+  if (checked) *checked = n;
+  return bad;
 }
 
 int craft_abi_version(void) { return CRAFT_ABI_VERSION; }

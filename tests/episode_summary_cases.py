@@ -30,8 +30,8 @@ RECT_LARGEST = "r15x16"              # the largest world the teachers accept: th
 OUTPUTS = ("length", "success", "end_pose", "distance", "actions", "flags")
 
 
-def make_sim(world, n, pool, T, device):
-    sim = CraftSim(world, n_envs=n, device=device, pool_capacity=max(1, len(pool)), max_timesteps=T)
+def make_sim(world, n, pool, T, device, **kw):
+    sim = CraftSim(world, n_envs=n, device=device, pool_capacity=max(1, len(pool)), max_timesteps=T, **kw)
     sim.load_pool(pool)
     return sim
 

@@ -3,6 +3,7 @@
 Run in the build container only (needs /root/reference, read-only):
     python tests/golden/make_golden.py
     python tests/golden/make_golden.py rect      # only rect_worlds.npz: worlds with WIDTH != HEIGHT
+    python tests/golden/make_golden.py limits    # only cookbook_limits.npz: the recipes.<name>.yaml cookbooks
 
 What it imports from the reference: worlds (CraftWorld/CraftState/Cookbook),
 data.task (TaskManager), teachers (DemonstrationTeacher), misc.util, and the
@@ -66,18 +67,18 @@ def import_reference():
 worlds, teachers, util, TaskManager = import_reference()
 
 
-def make_config(world_yaml="craft_medium", seed=123):
-    cfg = util.Struct(recipes="resources/craft/recipes.yaml",
+def make_config(world_yaml="craft_medium", seed=123, recipes=None, hints=None):
+    cfg = util.Struct(recipes=recipes or "resources/craft/recipes.yaml",
                       world={"name": "CraftWorld", "config": world_yaml},
                       student={"model": {}}, teacher={"name": "DemonstrationTeacher"},
-                      trainer={"hints": "resources/craft/hints.hierarchy.yaml", "batch_size": 32,
+                      trainer={"hints": hints or "resources/craft/hints.hierarchy.yaml", "batch_size": 32,
                                "max_timesteps": 40})
     cfg.random = np.random.RandomState(seed)
     return cfg
 
 
-def make_world(W=None, window=None, seed=123, H=None, prims=None):
-    cfg = make_config(seed=seed)
+def make_world(W=None, window=None, seed=123, H=None, prims=None, recipes=None, hints=None):
+    cfg = make_config(seed=seed, recipes=recipes, hints=hints)
     world = worlds.load(cfg)
     if W is not None:
         world.WIDTH, world.HEIGHT = W, (W if H is None else H)
@@ -201,9 +202,9 @@ def gen_scenarios():
     return arrays
 
 
-def scenario_arrays(arrays, name, W, H, count, prims=None):
+def scenario_arrays(arrays, name, W, H, count, prims=None, recipes=None, hints=None):
     """The first `count` de-duplicated sample_scenario worlds from RandomState(123)."""
-    cfg, world = make_world(W, H=H, prims=prims)
+    cfg, world = make_world(W, H=H, prims=prims, recipes=recipes, hints=hints)
     fns = make_data_functions(world)
     ingredients = [world.cookbook.index[i] for i in ["wood", "grass", "iron"]]
     grids, inits = [], []
@@ -220,11 +221,12 @@ def scenario_arrays(arrays, name, W, H, count, prims=None):
     arrays[f"{name}_mt_pos"] = np.asarray([st[2]], dtype=np.int32)
 
 
-def gen_rollout(w12_grids, window, T, E, P, all_obs_ticks, W=12, H=12, prims=None, save=True):
+def gen_rollout(w12_grids, window, T, E, P, all_obs_ticks, W=12, H=12, prims=None, save=True, recipes=None,
+                hints=None, max_timesteps=40):
     """Synthetic random-action rollouts through the reference's CraftState,
     with ImitationTrainer.do_rollout's per-env protocol (imitation.py:59-73)
     and auto-reset to the env's initial state."""
-    cfg, world = make_world(W, window, H=H, prims=prims)
+    cfg, world = make_world(W, window, H=H, prims=prims, recipes=recipes, hints=hints)
     tm = TaskManager(cfg)
     K = world.cookbook.n_kinds
     task_objs = list(tm.tasks)
@@ -247,7 +249,7 @@ def gen_rollout(w12_grids, window, T, E, P, all_obs_ticks, W=12, H=12, prims=Non
         return world.init_state(onehots[scen[e]], (xs[e], ys[e]), dirs[e])
 
     states = [init(e) for e in range(E)]
-    timer = [40] * E
+    timer = [max_timesteps] * E
     F = world.n_features
     rec = {k: [] for k in ["agent", "inv", "grid", "done", "success", "reward", "actions"]}
     obs_all = np.zeros((T, E, F), dtype=np.uint8)
@@ -261,7 +263,7 @@ def gen_rollout(w12_grids, window, T, E, P, all_obs_ticks, W=12, H=12, prims=Non
                 s = states[e].satisfies(task_objs[tasks[e]])
                 succ = int(bool(s))
                 states[e] = init(e)
-                timer[e] = 40
+                timer[e] = max_timesteps
             else:
                 _, states[e] = states[e].step(a)
                 succ = -1
@@ -300,10 +302,12 @@ def gen_rollout(w12_grids, window, T, E, P, all_obs_ticks, W=12, H=12, prims=Non
     print(name, os.path.getsize(os.path.join(OUT, name)))
 
 
-def random_state_cases(n, W, seed, H=None, window=None, prims=None):
-    """Random grids with the boundary ring and arbitrary interior kinds."""
+def random_state_cases(n, W, seed, H=None, window=None, prims=None, recipes=None, hints=None, top_kind=0):
+    """Random grids with the boundary ring and arbitrary interior kinds.  top_kind: the first
+    top_kind cases also hold the highest kind id, K-1, in the inventory and in the cell the agent
+    faces (where that cell is inside the ring)."""
     H = W if H is None else H
-    cfg, world = make_world(W, window, H=H, prims=prims)
+    cfg, world = make_world(W, window, H=H, prims=prims, recipes=recipes, hints=hints)
     tm = TaskManager(cfg)
     K = world.cookbook.n_kinds
     rng = np.random.RandomState(seed)
@@ -327,6 +331,12 @@ def random_state_cases(n, W, seed, H=None, window=None, prims=None):
         for k in rng.randint(1, K, size=nz):
             inv[k] += rng.randint(1, 3)
         a = rng.randint(6)
+        if i < top_kind:
+            inv[K - 1] += 1 + i % 3
+            fx, fy = x + (0, 0, -1, 1)[d], y + (-1, 1, 0, 0)[d]
+            if 0 < fx < W - 1 and 0 < fy < H - 1:
+                g[fx, fy] = K - 1
+            a = 4 if i % 2 == 0 else a
         cases.append((g, x, y, d, inv, a))
     return cfg, world, tm, cases
 
@@ -427,26 +437,35 @@ def gen_kat_edges():
     print("kat_edges.json", len(cases))
 
 
-def gen_teacher(w12_grids, n_states=400, W=12, H=12, window=None, prims=None, save=True):
+def gen_teacher(w12_grids, n_states=400, W=12, H=12, window=None, prims=None, save=True, recipes=None,
+                hints=None, items=None, sprinkle=()):
     """DemonstrationTeacher actions and find_closest_resources lengths on 12x12
     worlds, random positions/directions/inventories, every task."""
-    cfg, world = make_world(W, window, H=H, prims=prims)
+    cfg, world = make_world(W, window, H=H, prims=prims, recipes=recipes, hints=hints)
     tm = TaskManager(cfg)
     teacher = teachers.load(cfg)
     K = world.cookbook.n_kinds
     I = world.cookbook.index
     rng = np.random.RandomState(5)
-    items = ["wood", "grass", "iron", "plank", "stick", "axe", "rope", "bridge"]
+    if items is None:
+        items = ["wood", "grass", "iron", "plank", "stick", "axe", "rope", "bridge"]
+        removable = (7, 8, 9)
+    else:                                   # (a cookbook of tests/golden/recipes.<name>.yaml)
+        removable = tuple(sorted(world.cookbook.primitives))
     grids, agents, invs, acts, lens = [], [], [], [], []
     for i in range(n_states):
         g = w12_grids[rng.randint(len(w12_grids))].reshape(W, H).astype(np.int64).copy()
         # sometimes remove a resource (as grabbing does) to vary the targets
         for _ in range(rng.randint(0, 3)):
-            cells = [(x, y) for x in range(W) for y in range(H) if g[x, y] in (7, 8, 9)]
+            cells = [(x, y) for x in range(W) for y in range(H) if g[x, y] in removable]
             if cells:
                 x, y = cells[rng.randint(len(cells))]
                 g[x, y] = 0
         free = [(x, y) for x in range(1, W - 1) for y in range(1, H - 1) if g[x, y] == 0]
+        for name in sprinkle:               # kinds sample_scenario never places, as targets on the grid
+            if rng.randint(2):
+                x, y = free.pop(rng.randint(len(free)))
+                g[x, y] = I[name]
         x, y = free[rng.randint(len(free))]
         d = rng.randint(4)
         inv = np.zeros(K)
@@ -771,7 +790,46 @@ def gen_rect(n_kat=180, n_scen=24, n_teacher=120, E=24, T=50):
     print("rect_worlds.npz", os.path.getsize(path))
 
 
+# name -> (W, H, window, N_PRIMITIVES, kinds sprinkled on the teacher states' grids)
+COOKBOOKS = {"limits": (12, 12, 3, 2, ("crown", "plank", "glass", "torch", "rope", "gold")),
+             "k32compact": (10, 10, 5, 1, ("ladder",)),
+             "even": (15, 16, 7, 2, ()),
+             "tiny": (12, 12, 3, 2, ())}
+
+
+def gen_limits(n_kat=100, n_scen=12, n_teacher=40, E=16, T=30, max_timesteps=12):
+    """cookbook_limits.npz: the cookbooks tests/golden/recipes.<name>.yaml + hints.<name>.yaml
+    (COOKBOOKS: up to the ABI's 32 kinds, 16 recipes of 4 ingredients, 64 tasks of 4 subtasks), each
+    with the layouts of rect_worlds.npz under a "<name>_<fixture>_" prefix: kat_, scen_, teacher_
+    (every task) and rollout_ (max_timesteps 12, observations of every tick).  On the 32-kind
+    cookbooks kind 31 is on the grids, in the inventories and a target."""
+    arrays = {}
+    for name, (W, H, window, prims, sprinkle) in COOKBOOKS.items():
+        kw = dict(recipes=os.path.join(OUT, f"recipes.{name}.yaml"), hints=os.path.join(OUT, f"hints.{name}.yaml"))
+        cases = random_state_cases(n_kat, W, 2000 + len(name), H=H, window=window, prims=prims,
+                                   top_kind=12 if sprinkle else 0, **kw)
+        cb = cases[1].cookbook
+        assert cb.n_kinds == {"limits": 32, "k32compact": 32, "even": 22, "tiny": 12}[name]
+        kat_step_arrays(arrays, f"{name}_kat_", *cases)
+        scenario_arrays(arrays, f"{name}_scen", W, H, n_scen, prims=prims, **kw)
+        grids = arrays[f"{name}_scen_grids"]
+        items = [k for k in cb.index.ordered_contents if cb.index[k] not in cb.environment]
+        for k, v in gen_teacher(grids, n_teacher, W, H, window, prims, save=False, items=items, sprinkle=sprinkle,
+                                **kw).items():
+            arrays[f"{name}_teacher_{k}"] = v
+        for k, v in gen_rollout(grids, window, T, E, n_scen, None, W, H, prims, save=False,
+                                max_timesteps=max_timesteps, **kw).items():
+            arrays[f"{name}_rollout_{k}"] = v
+        print(name, "teacher actions", np.unique(arrays[f"{name}_teacher_action"], return_counts=True))
+    path = os.path.join(OUT, "cookbook_limits.npz")
+    np.savez_compressed(path, **arrays)
+    print("cookbook_limits.npz", os.path.getsize(path))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["limits"]:              # only the cookbook fixture
+        gen_limits()
+        sys.exit(0)
     if sys.argv[1:] == ["rect"]:                # only the WIDTH != HEIGHT fixture
         gen_rect()
         sys.exit(0)

@@ -5,10 +5,10 @@ from psketch_amd import gamedef
 from psketch_amd.cookbook import Cookbook, TaskManager, compile_config, world_params
 
 
-def make_tables(world="craft_medium", max_timesteps=gamedef.MAX_TIMESTEPS):
+def make_tables(world="craft_medium", max_timesteps=gamedef.MAX_TIMESTEPS, recipes=None, hints=None):
     params = world_params(world)
-    cb = Cookbook()
-    tm = TaskManager()
+    cb = Cookbook(recipes)
+    tm = TaskManager(hints)
     cfg = compile_config(params, cb, tm, max_timesteps)
     return params, cb, tm, cfg
 

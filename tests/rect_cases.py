@@ -177,10 +177,14 @@ def assert_state_equals_oracle(sim, envs, case):
     np.testing.assert_array_equal(host(st["grid"]), envs["grid"][:, :case.C])
 
 
-def run_lockstep(sim, case, oracle_mod, fmt="f32", T=45, teacher_at=(), autoreset=True, hashed_every=5):
+def run_lockstep(sim, case, oracle_mod, fmt="f32", T=45, teacher_at=(), autoreset=True, hashed_every=5,
+                 actions=mixed_actions, watch=None):
     """craft_step on `sim` against the oracle every tick: observation (in format fmt), reward,
     done, success; at the ticks of teacher_at also standalone craft_teacher of every env against
-    oracle.teacher; at the end agent / inventory / grid and stats."""
+    oracle.teacher; at the end agent / inventory / grid and stats.  actions: what draws the given
+    actions from the oracle's side (mixed_actions); watch: a further coverage object, told every
+    tick (tick(pre, acts, envs, done, autoreset, obs)) and teacher query (query(envs, labels)) of
+    the oracle's and checked at the end."""
     n, dev = case.n, sim.device
     sim.set_obs_format(fmt)
     sim.reset(*case.specs)
@@ -198,7 +202,7 @@ def run_lockstep(sim, case, oracle_mod, fmt="f32", T=45, teacher_at=(), autorese
         if hashed_every and t % hashed_every == hashed_every - 1:       # the in-kernel hashed draw
             given, acts = None, hash_actions(5, gids, t)
         else:
-            given = acts = mixed_actions(o, envs, rng)
+            given = acts = actions(o, envs, rng)
         sim.step(None if given is None else torch.as_tensor(given, device=dev), seed=5, tick=t,
                  autoreset=autoreset, obs=obs, reward=rew, done=done, success=succ)
         rc, oobs, orew, odone, osucc = o.batch_tick(envs, case.base, given, 5, t, autoreset, True, stats)
@@ -208,12 +212,16 @@ def run_lockstep(sim, case, oracle_mod, fmt="f32", T=45, teacher_at=(), autorese
         np.testing.assert_array_equal(host(rew), orew, err_msg=f"reward t={t}")
         np.testing.assert_array_equal(host(obs.float()), oobs, err_msg=f"obs t={t}")
         cov.tick(pre, acts, envs, odone, autoreset)
+        if watch is not None:
+            watch.tick(pre, acts, envs, odone, autoreset, oobs)
         if t in teacher_at:
             want = oracle_labels(o, envs)
             got, _ = sim.teacher()
             np.testing.assert_array_equal(host(got), want, err_msg=f"teacher t={t}")
             check_teacher_latch(sim, want)
             tcov.query(envs, want)
+            if watch is not None:
+                watch.query(envs, want)
             assert_state_equals_oracle(sim, envs, case)
     assert_state_equals_oracle(sim, envs, case)
     np.testing.assert_array_equal(host(sim.stats()), stats)
@@ -221,15 +229,18 @@ def run_lockstep(sim, case, oracle_mod, fmt="f32", T=45, teacher_at=(), autorese
     cov.check()
     if teacher_at:
         tcov.check()
+    if watch is not None:
+        watch.check()
     return cov, tcov
 
 
-def run_rollout(sim, case, oracle_mod, fmt="f32", launches=4, K=12, R=None, hashed=(1,)):
+def run_rollout(sim, case, oracle_mod, fmt="f32", launches=4, K=12, R=None, hashed=(1,), actions=mixed_actions,
+                watch=None):
     """craft_rollout on `sim`, `launches` launches of K ticks, against the oracle's per-tick
     results: every slot of the observation / reward / done / success rings after each launch (ring
     R ticks, default K: a shorter ring holds the launch's last R ticks), the state after each
     launch and stats.  The launches of `hashed` use the in-kernel hashed draw, the others a table
-    of mixed_actions."""
+    of `actions` (mixed_actions); watch as in run_lockstep."""
     n, dev = case.n, sim.device
     R = K if R is None else R
     sim.set_obs_format(fmt)
@@ -250,12 +261,14 @@ def run_rollout(sim, case, oracle_mod, fmt="f32", launches=4, K=12, R=None, hash
             if l in hashed:
                 given, acts = None, hash_actions(5, gids, t)
             else:
-                given = acts = mixed_actions(o, envs, rng)
+                given = acts = actions(o, envs, rng)
                 table.append(given)
             rc, *res = o.batch_tick(envs, case.base, given, 5, t, True, True, stats)
             assert rc == 0
             want[t % R] = (t, res)
             cov.tick(pre, acts, envs, res[2], True)
+            if watch is not None:
+                watch.tick(pre, acts, envs, res[2], True, res[0])
         sim.rollout(K, seed=5, tick0=l * K, actions=torch.as_tensor(np.stack(table), device=dev) if table else None,
                     autoreset=True, obs=obs, reward=rew, done=done, success=succ)
         for slot, (t, (oobs, orew, odone, osucc)) in want.items():
@@ -267,13 +280,15 @@ def run_rollout(sim, case, oracle_mod, fmt="f32", launches=4, K=12, R=None, hash
     np.testing.assert_array_equal(host(sim.stats()), stats)
     sim.check()
     cov.check()
+    if watch is not None:
+        watch.check()
     return cov
 
 
-def run_step_teach(sim, case, oracle_mod, T=30):
+def run_step_teach(sim, case, oracle_mod, T=30, watch=None):
     """craft_step_teach on `sim` (craft_step with labels): the label of every env every tick
     against oracle.teacher, the observation against the oracle; given actions with USE at about
-    35 %, so cells are cleared and queries leave the teacher table."""
+    35 %, so cells are cleared and queries leave the teacher table; watch as in run_lockstep."""
     n, dev = case.n, sim.device
     sim.reset(*case.specs)
     o, envs = oracle_envs(oracle_mod, case)
@@ -283,14 +298,20 @@ def run_step_teach(sim, case, oracle_mod, T=30):
     tcov = TeacherCoverage(case)
     for t in range(T):
         acts = rng.choice(6, size=n, p=[.15, .15, .15, .15, .38, .02]).astype(np.int32)
+        pre = envs.copy()
         sim.step(torch.as_tensor(acts, device=dev), seed=3, tick=t, autoreset=True, obs=obs, labels=lab)
-        rc, oobs, _, _, _ = o.batch_tick(envs, case.base, acts, 3, t, True, True, None)
+        rc, oobs, _, odone, _ = o.batch_tick(envs, case.base, acts, 3, t, True, True, None)
         assert rc == 0
         want = oracle_labels(o, envs)
+        if watch is not None:
+            watch.tick(pre, acts, envs, odone, True, oobs)
+            watch.query(envs, want)
         np.testing.assert_array_equal(host(lab), want, err_msg=f"labels t={t}")
         np.testing.assert_array_equal(host(obs.float()), oobs, err_msg=f"obs t={t}")
         check_teacher_latch(sim, want)
         tcov.query(envs, want)
     assert_state_equals_oracle(sim, envs, case)
     tcov.check()
+    if watch is not None:
+        watch.check()
     return tcov

@@ -14,8 +14,11 @@ Handles (Ctx), all tiny: 70 envs (not a multiple of any tile), a 4-row pool.
   queued  as base, with an episode queue installed but not begun
   begun   as queued, begun without wrap
   big     16x16 (4*W*H = 1024 > 1000), reset, its queue begun: the six BFS-queue refusals
+  k32w7   15x16, 7x7 window, the 32 kinds of tests/golden/recipes.limits.yaml, reset: the tile that
+          does not fit a workgroup's LDS
 """
 import ctypes
+import os
 from collections import namedtuple
 
 import numpy as np
@@ -28,7 +31,10 @@ from tests.helpers import make_tables, rect_world
 N_ENVS, POOL = 70, 4
 QUEUE = 3 * N_ENVS + 17
 WORLDS = {"base": "craft_medium_12x12", "w5": "craft_medium_12x12_w5", "queued": "craft_medium_12x12",
-          "begun": "craft_medium_12x12", "big": rect_world(16, 16, 3)}
+          "begun": "craft_medium_12x12", "big": rect_world(16, 16, 3), "k32w7": rect_world(15, 16, 7)}
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+COOKBOOKS = {"k32w7": dict(recipes=os.path.join(_GOLDEN, "recipes.limits.yaml"),
+                           hints=os.path.join(_GOLDEN, "hints.limits.yaml"))}
 
 Row = namedtuple("Row", "id entry handle call status message")
 
@@ -39,7 +45,8 @@ class Ctx:
 
     def __init__(self, name, device):
         world = WORLDS[name]
-        params, cb, tm, cfg = make_tables(world)
+        kw = COOKBOOKS.get(name, {})
+        params, cb, tm, cfg = make_tables(world, **kw)
         W, H = params["WIDTH"], params["HEIGHT"]
         self.name, self.cfg = name, cfg
         self.pool, _, _ = sample_scenarios(params, cb, 123, POOL)
@@ -47,7 +54,7 @@ class Ctx:
         self.specs = synthetic_specs(self.pool, W, H, N_ENVS, 0, seed=7, task_ids=tasks)
         self.queue = np.ascontiguousarray(
             np.stack(synthetic_specs(self.pool, W, H, QUEUE, 0, seed=9, task_ids=tasks), 1).astype(np.int32))
-        self.sim = sim = CraftSim(world, n_envs=N_ENVS, device=device, pool_capacity=POOL)
+        self.sim = sim = CraftSim(world, n_envs=N_ENVS, device=device, pool_capacity=POOL, **kw)
         sim.load_pool(self.pool)
         sim.reset(*self.specs)
         if name in ("queued", "begun", "big"):
@@ -120,6 +127,9 @@ _rows = [
      "craft_sim_tune: tile_envs must be 16, 32 or 64"),
     ("tune-tile-1", "craft_sim_tune", "w5", lambda c: c.sim.tune(-1, 0, 0), _E,
      "craft_sim_tune: tile_envs must be 16, 32 or 64"),
+    ("tune-tile64-k32w7", "craft_sim_tune", "k32w7", lambda c: c.sim.tune(64, 0, 2), _E,
+     "craft_sim_tune: a tile of tile_envs envs does not fit a workgroup's 160 KiB of LDS with this window and kind "
+     "count"),
     ("tune-resident2", "craft_sim_tune", "w5", lambda c: c.sim.tune(16, 2, 1), _E,
      "craft_sim_tune: max_resident_per_cu must be 0 or 3..32"),
     ("tune-resident33", "craft_sim_tune", "w5", lambda c: c.sim.tune(16, 33, 1), _E,

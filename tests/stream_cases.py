@@ -15,11 +15,12 @@ STREAM_OUTPUTS = ("obs", "reward", "done", "success", "action_record", "transiti
                   "episode_end", "end_pose", "episode_now")
 
 
-def queue_inputs(world, W, n, seed=11, pool_size=24, H=None):
+def queue_inputs(world, W, n, seed=11, pool_size=24, H=None, tables=None):
     """A pool of `pool_size` scenarios and a queue of 3n + 17 episode specs over it (not a
     multiple of n: slots run out on different ticks), in shuffled order so that a slot's
-    consecutive entries differ in scenario and task whatever n is, with every start direction."""
-    params, cb, tm, cfg = make_tables(world, T_MAX)
+    consecutive entries differ in scenario and task whatever n is, with every start direction.
+    tables: make_tables' result for a cookbook and task list other than the built-in ones."""
+    params, cb, tm, cfg = tables or make_tables(world, T_MAX)
     pool, _, _ = sample_scenarios(params, cb, 123, pool_size)
     count = 3 * n + 17
     specs = np.stack(synthetic_specs(pool, W, W if H is None else H, count, 0, seed=seed,

@@ -155,14 +155,14 @@ def test_random_step_kats_cpu(fx, tag):
     check_kats(fx, tag, "cpu")
 
 
-def check_kats(fx, tag, device):
+def check_kats(fx, tag, device, world=None, **kw):
     """craft_set_state / craft_observe / craft_transition / craft_get_state on slot lists against
-    the reference's features, satisfies and step of the fixture's random states."""
-    W, H, window, prims = RECT_SHAPES[tag]
+    the reference's features, satisfies and step of the fixture's random states (world: the
+    params of the fixture part `tag`, default RECT_SHAPES[tag]'s; kw: CraftSim's recipes, hints)."""
     p = f"{tag}_kat_"
     n = len(fx[p + "action"])
     dev = "cpu" if device == "cpu" else "cuda"
-    sim = CraftSim(rect_world(W, H, window, prims), n_envs=2 * n + 8, device=device, pool_capacity=n)
+    sim = CraftSim(world or rect_world(*RECT_SHAPES[tag]), n_envs=2 * n + 8, device=device, pool_capacity=n, **kw)
     sim.load_pool(fx[p + "pre_grid"])
     # the states go to the slots 2n+7 .. n+8 (a slot list, in reverse), the results to 0 .. n-1
     slots = torch.arange(2 * n + 7, n + 7, -1, dtype=torch.int32, device=dev)
@@ -244,17 +244,20 @@ def test_lockstep_vs_oracle_cpu(oracle_mod, tag):
 _teach_refs = {}
 
 
-def teach_reference(oracle_mod, tag, mode, n, launches, K, want_obs=False, seed=7):
+def teach_reference(oracle_mod, tag, mode, n, launches, K, want_obs=False, seed=7, make_case=rect_case,
+                    make_watch=None):
     """rollout_oracle.teach_rollout of `launches` launches of K ticks on rect_case(tag) in `mode`
     (policy = hashed draw; label = every env acts on its label, no auto-reset; bc = half the envs
-    act on their labels), chaining label_in; computed once per argument set and left unchanged.
+    act on their labels), chaining label_in; computed once per argument set and left unchanged
+    (make_case: what builds the case of `tag`, with rect_case's arguments; make_watch(case): a
+    further coverage object for rollout_oracle.teach_rollout's watch, checked here).
     Returns the case, the launch arguments, and per launch the oracle's outputs and a copy of its
     envs after it; asserts the teacher conditions of the run (TeacherCoverage)."""
     from oracle import rollout_oracle
-    key = (tag, mode, n, launches, K, want_obs, seed)
+    key = (tag, mode, n, launches, K, want_obs, seed, make_case, make_watch)
     if key in _teach_refs:
         return _teach_refs[key]
-    case = rect_case(oracle_mod, tag, n=n, seed=4, base=1000)
+    case = make_case(oracle_mod, tag, n=n, seed=4, base=1000)
     o, envs = oracle_envs(oracle_mod, case)
     lsrc = mode in ("label", "bc")
     bc = (np.random.RandomState(5).rand(n) < 0.5).astype(np.uint8) if mode == "bc" else None
@@ -262,18 +265,23 @@ def teach_reference(oracle_mod, tag, mode, n, launches, K, want_obs=False, seed=
     a = NS(seed=seed, autoreset=mode != "label", bc=bc, label_in=oracle_labels(o, envs) if lsrc else None,
            label_actions=mode == "label")
     cov = TeacherCoverage(case)
+    watch = make_watch(case) if make_watch else None
     if lsrc:
         cov.query(envs, a.label_in)
+        if watch is not None:
+            watch.query(envs, a.label_in)
     label_in, refs = a.label_in, []
     for l in range(launches):
         ref = rollout_oracle.teach_rollout(o, envs, np.arange(case.base, case.base + n), K, seed=seed, tick0=l * K,
                                            autoreset=a.autoreset, label_in=label_in, label_src=src,
-                                           want_obs=want_obs)
+                                           want_obs=want_obs, watch=watch)
         cov.values |= set(ref["labels"][ref["labels"] != -1].tolist())
         cov.query(envs, ref["labels"][-1])          # (the states of the launch's last query)
         label_in = ref["labels"][-1] if lsrc else None
         refs.append((ref, envs.copy()))
     a.coverage = cov
+    if watch is not None:
+        watch.check()
     _teach_refs[key] = (case, o, a, refs)
     return _teach_refs[key]
 
@@ -343,14 +351,14 @@ def check_pool_generate(oracle_mod, tag, device, count):
     return sim, grids, oinit
 
 
-def check_distances_vs_oracle(oracle_mod, tag, device):
+def check_distances_vs_oracle(oracle_mod, tag, device, make_case=rect_case, n=96, T=6, **kw):
     """craft_rollout_distances after a label-mode rollout without auto-reset, against the
     oracle's closest_resource from each env's final pose on its scenario's initial grid
     (trainers/imitation.py:79-91).  Returns the outputs."""
-    n, T = 96, 6                        # the nearer targets are reached, the farther ones are not
-    case, o, a, refs = teach_reference(oracle_mod, tag, "label", n, 1, T)
+    # (6 ticks: the nearer targets are reached, the farther ones are not)
+    case, o, a, refs = teach_reference(oracle_mod, tag, "label", n, 1, T, make_case=make_case)
     envs = refs[0][1]
-    sim = make_sim(case, device)
+    sim = make_sim(case, device, **kw)
     rec = check_teach_rollout(sim, case, a, refs, K=T, coverage=False)[0]["action_record"]
     dev = sim.device
     tasks = case.specs[4]
@@ -374,7 +382,8 @@ def check_distances_vs_oracle(oracle_mod, tag, device):
     np.testing.assert_array_equal(host(d), want)
     np.testing.assert_array_equal(host(ig), is_get.astype(np.uint8))
     np.testing.assert_array_equal(host(na), (host(rec) >= 0).sum(axis=0))
-    assert host(fl).tolist() == [0, int((want == -2).any())]
+    # (flag 1: a failed get whose grid holds no target, -1, or whose targets cannot be reached, -2)
+    assert host(fl).tolist() == [0, int(((want < 0) & is_get).any())]
     return [host(x) for x in (d, ig, na, fl)]
 
 
