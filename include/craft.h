@@ -507,6 +507,77 @@ typedef struct {
 } craft_lang_stream_step_args_t;
 int craft_step_lang_stream(craft_sim_t* sim, const craft_lang_stream_step_args_t* args, void* stream);
 
+/* ---- the policy head: the student's logits chosen inside the tick ----------------
+ * Between the student's last GEMM and the tick a caller otherwise runs small kernels only to turn
+ * [n_envs][6] logits into int32[n_envs] actions: argmax and a cast in evaluation
+ * (students/imitation.py:80), Categorical(logits).sample() in training (:82).  The entry points
+ * below take the logits and choose the action themselves, by a rule written out operation by
+ * operation so that both libraries (and any third implementation) give the same bits.
+ *
+ * The head rule.  Slot i has global id g = env_id_base + i; the tick is t; its row is the six
+ * floats l[0..5] = logits[6 * i ..].  All arithmetic is IEEE binary32, round to nearest even, no
+ * contraction other than the fmaf written here.
+ *   1. bad = some l[k] is NaN or +inf (that is, !(l[k] < +inf)).  m = the maximum of the six, taken
+ *      as m = l[0]; m = (l[k] > m) ? l[k] : m for k = 1..5.  If bad, or m == -inf, the action
+ *      is -1 and nothing below runs.
+ *   2. CRAFT_HEAD_ARGMAX: the action is the smallest k with l[k] == m (torch.argmax's documented
+ *      choice among equal maxima).
+ *   3. CRAFT_HEAD_SAMPLE:
+ *        h = splitmix64(seed ^ (g << 20) ^ t)     (uint64; the mixing of craft_step's hashed draw:
+ *            z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *            z = (z ^ z >> 27) * 0x94D049BB133111EB; h = z ^ z >> 31)
+ *        u = (float)(h >> 40) * 2^-24             (exact: 24 bits; 0 <= u < 1)
+ *        w[k] = 0 when l[k] == -inf, else craft_expf(max(l[k] - m, -80.0f))
+ *        c[0] = w[0]; c[k] = c[k-1] + w[k]        (float adds, in index order)
+ *        thr = u * c[5]
+ *        the action is the smallest k with c[k] > thr; if there is none (thr rounded up to c[5]),
+ *        the largest k with w[k] > 0.
+ *      A masked action (l[k] == -inf) is never drawn: c does not rise at it.  The -80 clamp keeps
+ *      every w a normal float (e^-80 = 1.8e-35), so denormal handling cannot differ anywhere.
+ *   craft_expf(x), for -80 <= x <= 0:
+ *        k = rintf(x * 1.44269502f)                               (0x3FB8AA3B)
+ *        r = fmaf(k, -0.693145752f, x)                            (0xBF317200: ln 2, high part)
+ *        r = fmaf(k, -1.42860677e-06f, r)                         (0xB5BFBE8E: ln 2, low part)
+ *        p = c6; p = fmaf(p, r, c5); ... ; p = fmaf(p, r, c0)     (Horner, degree 6)
+ *          c6..c0, as float bit patterns: 0x3AB566C5, 0x3C0936C6, 0x3D2AAC3F, 0x3E2AAA05,
+ *          0x3EFFFFFD, 0x3F800000, 0x3F800000
+ *        the result is the float whose bits are bits(p) + ((int32)k << 23)   (p in [0.70, 1.42],
+ *        k >= -116: the exponent field never leaves the normal range)
+ *      No library exp, no fast-math.  Within 2^-21 relative of exp(x) on [-80, 0].
+ * An action of -1 is treated exactly as actions[i] = -1 is under the wrapped entry point: a
+ * running slot latches CRAFT_EBADACTION (unless STOP's test or the time limit ends its episode
+ * first, as for a given -1), and a slot with behavior_clone set acts on its label instead.
+ * CRAFT_EINVAL for every entry point below (the message names it): a NULL head or NULL
+ * head->logits, a mode other than the two, a logits base that is not 8-byte aligned. */
+#define CRAFT_HEAD_ARGMAX 0
+#define CRAFT_HEAD_SAMPLE 1
+typedef struct {
+  const float* logits;  /* device fp32 [n_envs][6], contiguous rows, base 8-byte aligned */
+  int32_t mode;         /* CRAFT_HEAD_* */
+  uint64_t seed;        /* SAMPLE only */
+} craft_policy_head_t;
+
+/* The head alone, one small launch: actions_out (device int32[n_envs]) = head(i) at `tick`.
+ * CRAFT_EINVAL also for a NULL actions_out. */
+int craft_policy_actions(craft_sim_t* sim, const craft_policy_head_t* head, int64_t tick,
+                         int32_t* actions_out, void* stream);
+
+/* craft_step_ex (label_out NULL) or craft_step_teach (label_out set) with actions[i] = head(i) at
+ * step->tick, in the same single launch: the kernels read the row beside the slot's state and run
+ * the head where they would draw the hashed action.  Every output, the slot state, the statistics
+ * and the latched error are those of craft_policy_actions followed by the wrapped entry point on
+ * its result.  CRAFT_EINVAL: the head's refusals above; step->actions != NULL (the actions are the
+ * head's); then everything the wrapped entry point refuses, with its message.  Launch shapes and
+ * knobs as the wrapped entry point (craft_sim_step_shape). */
+int craft_step_policy(craft_sim_t* sim, const craft_step_args_t* step, const craft_policy_head_t* head,
+                      int32_t* label_out, void* stream);
+
+/* craft_step_stream likewise: args->step.actions must be NULL, actions[i] = head(i) at
+ * args->step.tick.  The head's action is known before the tick decides whether the slot's episode
+ * ends, so the fetch of the next queue entry is issued as early as with given actions. */
+int craft_step_policy_stream(craft_sim_t* sim, const craft_stream_step_args_t* args,
+                             const craft_policy_head_t* head, void* stream);
+
 /* n_ticks consecutive craft_step ticks (tick0, tick0+1, ...) in one launch, with
  * results identical to n_ticks craft_step calls: each workgroup keeps its envs
  * on chip between ticks, so the per-tick prologue overlaps other workgroups'

@@ -36,6 +36,9 @@ GOAL_OTHER, GOAL_GET, GOAL_MAKE, GOAL_GO, GOAL_USE = range(5)
 STEP_AUTORESET = 1
 QUEUE_WRAP = 1
 
+HEAD_ARGMAX, HEAD_SAMPLE = 0, 1
+HEAD_MODES = {"argmax": HEAD_ARGMAX, "sample": HEAD_SAMPLE}
+
 KERNEL_TILE, KERNEL_TICK2 = 1, 2
 KERNEL_NAMES = {KERNEL_TILE: "tile_kernel", KERNEL_TICK2: "tick2_kernel"}
 
@@ -124,6 +127,14 @@ class craft_stream_step_args_t(ctypes.Structure):
         ("episode_end", ctypes.c_void_p),
         ("end_pose", ctypes.c_void_p),
         ("episode_now", ctypes.c_void_p),
+    ]
+
+
+class craft_policy_head_t(ctypes.Structure):
+    _fields_ = [
+        ("logits", ctypes.c_void_p),
+        ("mode", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
     ]
 
 
@@ -249,6 +260,11 @@ SIGNATURES = {
     "craft_step": (_i32, [_vp, _vp, _u64, _i64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "craft_step_ex": (_i32, [_vp, ctypes.POINTER(craft_step_args_t), _vp]),
     "craft_step_teach": (_i32, [_vp, ctypes.POINTER(craft_step_args_t), _vp, _vp]),
+    "craft_policy_actions": (_i32, [_vp, ctypes.POINTER(craft_policy_head_t), _i64, _vp, _vp]),
+    "craft_step_policy": (_i32, [_vp, ctypes.POINTER(craft_step_args_t), ctypes.POINTER(craft_policy_head_t),
+                                 _vp, _vp]),
+    "craft_step_policy_stream": (_i32, [_vp, ctypes.POINTER(craft_stream_step_args_t),
+                                        ctypes.POINTER(craft_policy_head_t), _vp]),
     "craft_step_lang": (_i32, [_vp, ctypes.POINTER(craft_lang_step_args_t), _vp]),
     "craft_episode_queue": (_i32, [_vp, _vp, _i64]),
     "craft_episode_begin": (_i32, [_vp, _i64, _i64, _u32, _vp, _vp]),

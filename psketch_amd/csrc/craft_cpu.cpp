@@ -21,9 +21,11 @@
 #include <algorithm>
 #include <atomic>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -31,6 +33,7 @@
 
 #include "craft_checks_episode_summary.h"
 #include "craft_checks_lang_stream.h"
+#include "craft_checks_policy.h"
 #include "craft_checks_rollout_replay.h"
 #include "craft_checks_rollout_stream.h"
 #include "craft_checks_rollout_teach_stream.h"
@@ -500,6 +503,70 @@ int hashed_action(const craft_sim* s, uint64_t seed, int64_t slot, int64_t tick)
   return (int)((uint32_t)(splitmix64(seed ^ ((uint64_t)(s->env_base + slot) << 20) ^ (uint64_t)tick) >> 32) % 6u);
 }
 
+// ---- the policy head (include/craft.h "The head rule"), this library's own copy: the HIP
+// library's is craft_policy.h, and the two agree bit for bit -------------------------------------
+float bits_float(uint32_t u) {
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+
+// e^x for -80 <= x <= 0.  std::fmaf is a single rounding whether or not the machine has the
+// instruction; x * c and the adds below stand alone, so nothing here can be contracted.
+float craft_expf(float x) {
+  const float k = std::rintf(x * bits_float(0x3FB8AA3Bu));
+  float r = std::fmaf(k, bits_float(0xBF317200u), x);
+  r = std::fmaf(k, bits_float(0xB5BFBE8Eu), r);
+  float p = bits_float(0x3AB566C5u);
+  p = std::fmaf(p, r, bits_float(0x3C0936C6u));
+  p = std::fmaf(p, r, bits_float(0x3D2AAC3Fu));
+  p = std::fmaf(p, r, bits_float(0x3E2AAA05u));
+  p = std::fmaf(p, r, bits_float(0x3EFFFFFDu));
+  p = std::fmaf(p, r, 1.0f);
+  p = std::fmaf(p, r, 1.0f);
+  uint32_t b;
+  std::memcpy(&b, &p, 4);
+  return bits_float(b + ((uint32_t)(int32_t)k << 23));
+}
+
+int policy_head(const float* l, int32_t mode, uint64_t seed, uint64_t gid, int64_t tick) {
+  const float inf = std::numeric_limits<float>::infinity();
+  bool bad = !(l[0] < inf);
+  float m = l[0];
+  for (int k = 1; k < 6; ++k) {
+    bad = bad || !(l[k] < inf);
+    m = (l[k] > m) ? l[k] : m;
+  }
+  if (bad || m == -inf) return -1;
+  if (mode == CRAFT_HEAD_ARGMAX) {
+    for (int k = 0; k < 6; ++k)
+      if (l[k] == m) return k;
+  }
+  const uint64_t h = splitmix64(seed ^ (gid << 20) ^ (uint64_t)tick);
+  const float u = (float)(uint32_t)(h >> 40) * bits_float(0x33800000u);   // 2^-24
+  float w[6], c[6];
+  for (int k = 0; k < 6; ++k) {
+    const float d = l[k] - m;
+    w[k] = (l[k] == -inf) ? 0.0f : craft_expf(d > -80.0f ? d : -80.0f);
+    c[k] = k == 0 ? w[0] : c[k - 1] + w[k];
+  }
+  const float thr = u * c[5];
+  for (int k = 0; k < 6; ++k)
+    if (c[k] > thr) return k;
+  int last = 0;
+  for (int k = 1; k < 6; ++k)
+    if (w[k] > 0.0f) last = k;
+  return last;
+}
+
+// head(i) of every slot into `out` (craft_policy_actions, and the actions of craft_step_policy*).
+void policy_actions(craft_sim* s, const craft_policy_head_t* h, int64_t tick, int32_t* out) {
+  parallel_for(s, s->n_envs, [&](int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i)
+      out[i] = policy_head(h->logits + 6 * i, h->mode, h->seed, (uint64_t)(s->env_base + i), tick);
+  });
+}
+
 // A slot reset / set_state has initialised: an interior position on a loaded pool row.
 bool slot_valid(const craft_sim* s, const Agent& a) {
   return a.x >= 1 && a.x <= s->W - 2 && a.y >= 1 && a.y <= s->H - 2 && a.scen < s->pool_count;
@@ -955,6 +1022,27 @@ int craft_step_teach(craft_sim_t* s, const craft_step_args_t* x, int32_t* label_
   return run_ticks(s, in, x->any_live);
 }
 
+int craft_policy_actions(craft_sim_t* s, const craft_policy_head_t* head, int64_t tick, int32_t* actions_out,
+                         void* /*stream*/) {
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_policy_actions(head, actions_out, s->last_error)) return rc;
+  policy_actions(s, head, tick, actions_out);
+  return CRAFT_OK;
+}
+
+// The wrapped entry point on the head's actions: this library runs the head as a pass of its own
+// (it is the implementation the fused kernels are checked against).
+int craft_step_policy(craft_sim_t* s, const craft_step_args_t* x, const craft_policy_head_t* head, int32_t* label_out,
+                      void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_step_policy(facts(s), x, head, label_out, s->last_error)) return rc;
+  std::vector<int32_t> actions((size_t)s->n_envs);
+  policy_actions(s, head, x->tick, actions.data());
+  craft_step_args_t y = *x;
+  y.actions = actions.data();
+  return label_out ? craft_step_teach(s, &y, label_out, stream) : craft_step_ex(s, &y, stream);
+}
+
 // One tick of the language trainers' loop (trainers/primitive_language.py:45-66 and its
 // interactive / active variants) for every slot: step first, then the timer and done, success
 // read off the new state, the teacher on every slot that was running before the tick.
@@ -1166,6 +1254,17 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* /
   });
   tot.commit(s, p.any_live);
   return CRAFT_OK;
+}
+
+int craft_step_policy_stream(craft_sim_t* s, const craft_stream_step_args_t* x, const craft_policy_head_t* head,
+                             void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_step_policy_stream(facts(s), x, head, s->last_error)) return rc;
+  std::vector<int32_t> actions((size_t)s->n_envs);
+  policy_actions(s, head, x->step.tick, actions.data());
+  craft_stream_step_args_t y = *x;
+  y.step.actions = actions.data();
+  return craft_step_stream(s, &y, stream);
 }
 
 // The language trainers' tick on the queue, written out on its own as well: the step comes first,

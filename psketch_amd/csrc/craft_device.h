@@ -33,8 +33,14 @@ constexpr int kInvStride = 36;     // LDS bytes per inventory row (9 dwords: ban
 // MODE_LANG: the language trainers' tick (craft_step_lang): step first, then the timer
 // MODE_STREAM: MODE_TICK whose auto-reset takes the slot's next episode-queue entry (craft_step_stream)
 // MODE_LANG_STREAM: MODE_LANG on the episode queue: the ending tick steps, then the slot restarts (craft_step_lang_stream)
+// MODE_TICK_HEAD, MODE_STREAM_HEAD: MODE_TICK / MODE_STREAM whose action is the policy head's (craft_step_policy,
+// craft_step_policy_stream; craft_policy.h): instantiations of their own, the two base modes' code is untouched
 enum Mode { MODE_TICK = 0, MODE_TRANSITION = 1, MODE_OBSERVE = 2, MODE_RESET = 3, MODE_LANG = 4, MODE_STREAM = 5,
-            MODE_LANG_STREAM = 6 };
+            MODE_LANG_STREAM = 6, MODE_TICK_HEAD = 7, MODE_STREAM_HEAD = 8 };
+__host__ __device__ constexpr bool mode_has_head(int mode) { return mode == MODE_TICK_HEAD || mode == MODE_STREAM_HEAD; }
+__host__ __device__ constexpr int mode_base(int mode) {
+  return mode == MODE_TICK_HEAD ? (int)MODE_TICK : mode == MODE_STREAM_HEAD ? (int)MODE_STREAM : mode;
+}
 
 struct SimView {
   const uint8_t* pool;
@@ -255,6 +261,11 @@ struct TileArgs {
   int32_t* ep_end;
   int32_t* end_pose;
   int32_t* ep_now;
+  // the policy head (MODE_TICK_HEAD, MODE_STREAM_HEAD and tick2_kernel<3 + kTick2Head>; craft_policy.h), appended likewise:
+  // fp32 [n][6] logits (8-byte aligned), CRAFT_HEAD_*, the SAMPLE draw's seed
+  const float* logits;
+  uint64_t head_seed;
+  int32_t head_mode;
 };
 
 struct RolloutArgs {       // craft_rollout: n_ticks ticks in one launch

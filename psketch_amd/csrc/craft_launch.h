@@ -8,16 +8,26 @@ namespace craft {
 // craft_tile.hip
 hipError_t launch_tile(int mode, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
                        hipStream_t st);
-// craft_tick_teach.hip
+// craft_tick_teach.hip (head: the policy head's instantiations, a.logits set)
 hipError_t launch_tick_teach(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                             hipStream_t st);
-hipError_t launch_tick2(int tl, int nw, const SimView& v, const TileArgs& a, size_t lds, hipStream_t st);
+                             hipStream_t st, bool head = false);
+hipError_t launch_tick2(int tl, int nw, const SimView& v, const TileArgs& a, size_t lds, hipStream_t st,
+                        bool head = false);
 size_t tick2_lds_bytes(int tl, int nw, int GS, int F);
 // craft_tick_lang.hip, craft_tick_stream.hip: tl = 0 launches the bare tick
 hipError_t launch_tick_lang(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
                             hipStream_t st);
 hipError_t launch_tick_stream(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                              hipStream_t st);
+                              hipStream_t st, bool head = false);
+// craft_tick_policy.hip, craft_tick_policy_stream.hip: where the three launchers above (and launch_tile's
+// MODE_TICK_HEAD) find the tile kernel's policy-head instantiations (tl = 0: the bare tick), and
+// craft_policy_actions' kernel
+hipError_t launch_tick_head(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
+                            hipStream_t st);
+hipError_t launch_tick_stream_head(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a,
+                                   size_t lds, hipStream_t st);
+hipError_t launch_policy_actions(const float* logits, int32_t mode, uint64_t seed, int64_t gid0, int64_t tick,
+                                 int64_t n, int32_t* actions_out, hipStream_t st);
 // craft_tick_lang_stream.hip
 hipError_t launch_tick_lang_stream(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
                                    hipStream_t st);

@@ -17,6 +17,7 @@
 #include "craft_device.h"
 #include "craft_checks_episode_summary.h"
 #include "craft_checks_lang_stream.h"
+#include "craft_checks_policy.h"
 #include "craft_checks_rollout_replay.h"
 #include "craft_checks_rollout_stream.h"
 #include "craft_checks_rollout_teach_stream.h"
@@ -560,6 +561,56 @@ int launch_tile_units(craft_sim_t* s, int tile, craft::RolloutArgs& a, void* str
   return CRAFT_OK;
 }
 
+// The three one-tick launches of (checked) arguments, each shared by an entry point and its
+// craft_step_policy* twin: `head` null = the actions are given or hashed, else the policy head's
+// (the same launchers and tick plan, the kernels' head instantiations).
+void head_args(const craft_policy_head_t* head, TileArgs& a) {
+  if (!head) return;
+  a.logits = head->logits;
+  a.head_mode = head->mode;
+  a.head_seed = head->seed;
+}
+
+int run_step(craft_sim_t* s, const craft_step_args_t* x, const craft_policy_head_t* head, void* stream) {
+  TileArgs a = step_args(s, x);
+  head_args(head, a);
+  return launch(s, head ? craft::MODE_TICK_HEAD : craft::MODE_TICK, a, stream, "craft_step launch");
+}
+
+int run_step_teach(craft_sim_t* s, const craft_step_args_t* x, const craft_policy_head_t* head, int32_t* label_out,
+                   void* stream, const char* what) {
+  TileArgs a = step_args(s, x);
+  a.label = label_out;
+  head_args(head, a);
+  int kernel = 0, envs = 0, tl = 0;
+  step_shape(s, true, &kernel, &envs, &tl);
+  TickPlan p;
+  const int rc = tick_plan(s, true, stream, what, p);
+  if (rc != CRAFT_OK) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const hipError_t e =
+      kernel == 2 ? craft::launch_tick2(tl, p.nw, p.v, a, craft::tick2_lds_bytes(tl, p.nw, s->view.GS, s->view.F), st,
+                                        head != nullptr)
+                  : craft::launch_tick_teach(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds, st, head != nullptr);
+  if (e != hipSuccess) return hip_fail(s, e, (std::string(what) + " launch").c_str());
+  return CRAFT_OK;
+}
+
+int run_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, const craft_policy_head_t* head, void* stream,
+                    const char* what) {
+  TileArgs a = step_args(s, &x->step);
+  a.label = x->label_out;
+  queue_args(s, *x, a);
+  head_args(head, a);
+  TickPlan p;
+  const int rc = tick_plan(s, x->label_out != nullptr, stream, what, p);
+  if (rc != CRAFT_OK) return rc;
+  const hipError_t e = craft::launch_tick_stream(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
+                                                 reinterpret_cast<hipStream_t>(stream), head != nullptr);
+  if (e != hipSuccess) return hip_fail(s, e, (std::string(what) + " launch").c_str());
+  return CRAFT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1015,19 +1066,31 @@ int craft_step_teach(craft_sim_t* s, const craft_step_args_t* x, int32_t* label_
   if (!s || !x || !label_out) return CRAFT_EINVAL;
   int rc = craft_host::check_step_teach(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
-  TileArgs a = step_args(s, x);
-  a.label = label_out;
-  int kernel = 0, envs = 0, tl = 0;
-  step_shape(s, true, &kernel, &envs, &tl);
-  TickPlan p;
-  rc = tick_plan(s, true, stream, "craft_step_teach", p);
-  if (rc != CRAFT_OK) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const hipError_t e =
-      kernel == 2 ? craft::launch_tick2(tl, p.nw, p.v, a, craft::tick2_lds_bytes(tl, p.nw, s->view.GS, s->view.F), st)
-                  : craft::launch_tick_teach(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds, st);
-  if (e != hipSuccess) return hip_fail(s, e, "craft_step_teach launch");
+  return run_step_teach(s, x, nullptr, label_out, stream, "craft_step_teach");
+}
+
+int craft_policy_actions(craft_sim_t* s, const craft_policy_head_t* head, int64_t tick, int32_t* actions_out,
+                         void* stream) {
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_policy_actions(head, actions_out, s->last_error)) return rc;
+  const hipError_t e = craft::launch_policy_actions(head->logits, head->mode, head->seed, s->env_base, tick, s->n_envs,
+                                                    actions_out, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(s, e, "craft_policy_actions launch");
   return CRAFT_OK;
+}
+
+int craft_step_policy(craft_sim_t* s, const craft_step_args_t* x, const craft_policy_head_t* head, int32_t* label_out,
+                      void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_step_policy(facts(s), x, head, label_out, s->last_error)) return rc;
+  return label_out ? run_step_teach(s, x, head, label_out, stream, "craft_step_policy") : run_step(s, x, head, stream);
+}
+
+int craft_step_policy_stream(craft_sim_t* s, const craft_stream_step_args_t* x, const craft_policy_head_t* head,
+                             void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_step_policy_stream(facts(s), x, head, s->last_error)) return rc;
+  return run_step_stream(s, x, head, stream, "craft_step_policy_stream");
 }
 
 int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* stream) {
@@ -1117,16 +1180,7 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* s
   if (!s || !x) return CRAFT_EINVAL;
   int rc = craft_host::check_step_stream(facts(s), x, s->last_error);
   if (rc != CRAFT_OK) return rc;
-  TileArgs a = step_args(s, &x->step);
-  a.label = x->label_out;
-  queue_args(s, *x, a);
-  TickPlan p;
-  rc = tick_plan(s, x->label_out != nullptr, stream, "craft_step_stream", p);
-  if (rc != CRAFT_OK) return rc;
-  const hipError_t e = craft::launch_tick_stream(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
-                                                 reinterpret_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return hip_fail(s, e, "craft_step_stream launch");
-  return CRAFT_OK;
+  return run_step_stream(s, x, nullptr, stream, "craft_step_stream");
 }
 
 int craft_step_lang_stream(craft_sim_t* s, const craft_lang_stream_step_args_t* x, void* stream) {
@@ -1147,7 +1201,7 @@ int craft_step_lang_stream(craft_sim_t* s, const craft_lang_stream_step_args_t* 
 int craft_step_ex(craft_sim_t* s, const craft_step_args_t* x, void* stream) {
   if (!s || !x) return CRAFT_EINVAL;
   if (const int rc = craft_host::check_step(x, s->last_error)) return rc;
-  return launch(s, craft::MODE_TICK, step_args(s, x), stream, "craft_step launch");
+  return run_step(s, x, nullptr, stream);
 }
 
 int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, int64_t tick0,

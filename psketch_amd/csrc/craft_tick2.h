@@ -29,6 +29,7 @@
 #pragma once
 #include "craft_episode.h"
 #include "craft_obs.h"
+#include "craft_policy.h"
 #include "craft_teach.h"
 
 namespace craft {
@@ -70,8 +71,15 @@ __host__ __device__ inline Tick2Lds tick2_lds(int J, int TW, int GS, int F, int 
 #define CRAFT_T2_U 4            // 16-byte stores in flight per lane of a tick wave's E
 #endif
 // TW tick waves (4 or 8): D + E of 64 / TW envs per tile each.
-template <int WIN, int J, int TW, int TL, int NW>
+// WINX = the window, plus kTick2Head for craft_step_policy's instantiations: the action is the
+// policy head's (craft_policy.h: the row's 24 bytes requested in the state's batch, the head where
+// the hashed draw runs).  A flag inside an existing argument, as tile_kernel's head modes are, so
+// that craft_step_teach's instantiations keep their names and their code.
+constexpr int kTick2Head = 16;
+template <int WINX, int J, int TW, int TL, int NW>
 __global__ __launch_bounds__(64 * TW + J * kTick2Tile * TL, CRAFT_T2_WPE) void tick2_kernel(SimView v, TileArgs a) {
+  constexpr int WIN = WINX & (kTick2Head - 1);
+  constexpr bool HEAD = (WINX & kTick2Head) != 0;
   constexpr int kTick2Waves = TW, kTick2Sub = kTick2Tile / TW;
   static_assert(J >= 1 && J < TW, "A + C runs on the first J tick waves, the rest zero the rows");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -130,6 +138,7 @@ __global__ __launch_bounds__(64 * TW + J * kTick2Tile * TL, CRAFT_T2_WPE) void t
     uint64_t st = 0;
     uint4 i0 = make_uint4(0, 0, 0, 0), i1 = i0, m0 = i0, m1 = i0;
     Agent s{};
+    LogitRow lrow{};                                                     // HEAD: the slot's logits
     // every independent load first, no result used before the last is issued (a wave waits for
     // its loads in issue order): one round trip, then the scenario row
     if (live) {
@@ -139,7 +148,8 @@ __global__ __launch_bounds__(64 * TW + J * kTick2Tile * TL, CRAFT_T2_WPE) void t
       m0 = v.mask[2 * slot];
       m1 = v.mask[2 * slot + 1];
       init_word = v.init[slot];
-      if (a.actions) act = a.actions[slot];
+      if constexpr (HEAD) lrow = load_logit_row(a.logits, slot);
+      else if (a.actions) act = a.actions[slot];
       if (a.bc) {
         bc = a.bc[slot];
         ref = a.ref[slot];
@@ -166,7 +176,8 @@ __global__ __launch_bounds__(64 * TW + J * kTick2Tile * TL, CRAFT_T2_WPE) void t
         if (lane + 64 * q < v.n_tasks * CRAFT_MAX_SUBTASKS) s_tsub[lane + 64 * q] = sw[q];
     }
     if (live) {
-      if (!a.actions) act = hashed_action(v, a.seed, slot, a.tick);
+      if constexpr (HEAD) act = policy_head(lrow, a.head_mode, a.head_seed, (uint64_t)(v.env_base + slot), a.tick);
+      else if (!a.actions) act = hashed_action(v, a.seed, slot, a.tick);
       asm volatile("" : "+v"(bc), "+v"(ref));                          // (no early wait on the flag)
       if (a.bc && (bc & 0xffu)) act = ref;                             // behaviour cloning, imitation.py:56-57
       s = unpack_state(st);

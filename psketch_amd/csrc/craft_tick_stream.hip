@@ -61,8 +61,10 @@ hipError_t launch_queue_begin(const uint2* entries, int64_t count, int64_t first
 }
 
 // tl = teacher lanes per env (1, 2 or 4), or 0: no teacher in the launch (tile 16, 32 or 64).
+// head: the policy head's instantiations (a.logits set; craft_tick_policy_stream.hip).
 hipError_t launch_tick_stream(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                              hipStream_t st) {
+                              hipStream_t st, bool head) {
+  if (head) return launch_tick_stream_head(tl, nw, win, tile, v, a, lds, st);
   if (tl == 0) return launch_tile_bare<MODE_STREAM>(win, tile, v, a, lds, st);
   return launch_tile_teach<MODE_STREAM>(tl, nw, win, tile, v, a, lds, st);
 }

@@ -11,8 +11,10 @@
 
 namespace craft {
 
+// head (here and in launch_tick2): the policy head's instantiations (a.logits set)
 hipError_t launch_tick_teach(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                             hipStream_t st) {
+                             hipStream_t st, bool head) {
+  if (head) return launch_tick_head(tl, nw, win, tile, v, a, lds, st);             // (craft_tick_policy.hip)
   return launch_tile_teach<MODE_TICK>(tl, nw, win, tile, v, a, lds, st);
 }
 
@@ -25,24 +27,28 @@ size_t tick2_lds_bytes(int tl, int nw, int GS, int F) {
   return (size_t)tick2_lds(kTick2Tiles, kTick2TickWaves, GS, F, nbuf).bytes;
 }
 
-template <int TL, int NW>
+template <auto KERNEL, int TL>
 static hipError_t launch_t2(const SimView& v, const TileArgs& a, size_t lds, hipStream_t st) {
   constexpr int TW = kTick2TickWaves;
   const int64_t per = (int64_t)kTick2Tiles * kTick2Tile;
   const int64_t blocks = (a.n + per - 1) / per;
   if (blocks == 0) return hipSuccess;
   // the teacher waves' own rows (tick2_share) pass 64 KiB
-  const hipError_t e = ensure_lds<&tick2_kernel<3, kTick2Tiles, TW, TL, NW>>(lds);
+  const hipError_t e = ensure_lds<KERNEL>(lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((tick2_kernel<3, kTick2Tiles, TW, TL, NW>), dim3((unsigned)blocks),
-                     dim3(64 * TW + kTick2Tiles * kTick2Tile * TL), lds, st, v, a);
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)blocks), dim3(64 * TW + kTick2Tiles * kTick2Tile * TL), lds, st, v, a);
   return hipGetLastError();
 }
 
-hipError_t launch_tick2(int tl, int nw, const SimView& v, const TileArgs& a, size_t lds, hipStream_t st) {
+hipError_t launch_tick2(int tl, int nw, const SimView& v, const TileArgs& a, size_t lds, hipStream_t st, bool head) {
+  constexpr int J = kTick2Tiles, TW = kTick2TickWaves;
   return dispatch_nw(nw, [&](auto nwc) {
     constexpr int NW = decltype(nwc)::value;
-    return tl == 4 ? launch_t2<4, NW>(v, a, lds, st) : launch_t2<2, NW>(v, a, lds, st);
+    if (head)
+      return tl == 4 ? launch_t2<&tick2_kernel<3 + kTick2Head, J, TW, 4, NW>, 4>(v, a, lds, st)
+                     : launch_t2<&tick2_kernel<3 + kTick2Head, J, TW, 2, NW>, 2>(v, a, lds, st);
+    return tl == 4 ? launch_t2<&tick2_kernel<3, J, TW, 4, NW>, 4>(v, a, lds, st)
+                   : launch_t2<&tick2_kernel<3, J, TW, 2, NW>, 2>(v, a, lds, st);
   });
 }
 

@@ -19,6 +19,7 @@
 #pragma once
 #include "craft_episode.h"
 #include "craft_obs.h"
+#include "craft_policy.h"
 #include "craft_teach.h"
 
 namespace craft {
@@ -53,8 +54,15 @@ namespace craft {
 // workgroups stopped at three per CU, 70.6 against 60 us for the bare tick at 5x5).
 __host__ __device__ constexpr int tile_tick_threads(int tile, int tl) { return tl > 0 && tile == 32 ? 192 : kThreads; }
 
-template <int WIN, int MODE, int TILE, int TL = 0, int NW = 0>
+//
+// MODE_TICK_HEAD / MODE_STREAM_HEAD (craft_step_policy, craft_step_policy_stream) are MODE_TICK /
+// MODE_STREAM whose action is the policy head's (craft_policy.h): the slot's 24 bytes of logits
+// are requested where the given action is, in the same batch, and the head's arithmetic runs
+// where the hashed draw does.  kHead is false in every other instantiation, whose code is as before.
+template <int WIN, int MODEX, int TILE, int TL = 0, int NW = 0>
 __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? CRAFT_TT_WPE : 1) void tile_kernel(SimView v, TileArgs a) {
+  constexpr int MODE = mode_base(MODEX);
+  constexpr bool kHead = mode_has_head(MODEX);
   constexpr int NT = tile_tick_threads(TILE, TL);
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const LdsLayout lay = lds_layout(TILE, v.GS, v.F);
@@ -121,9 +129,11 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
     // (MODE_STREAM: the cursor and the action first.  With the state word they say whether the
     // episode ends, and the fetch of the next queue entry and the row loads behind it then wait
     // for these and the state, not for the inventory and the mask queued after them)
+    LogitRow lrow{};                                       // kHead: the slot's logits
     if (kQueue && live) {
       cur = a.q_cursor[slot];
-      if (a.actions) act = a.actions[slot];
+      if constexpr (kHead) lrow = load_logit_row(a.logits, slot);
+      else if (a.actions) act = a.actions[slot];
       if (a.bc) {
         bc = a.bc[slot];
         ref = a.ref[slot];
@@ -137,7 +147,8 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       m1 = v.mask[2 * slot + 1];
       if (MODE == MODE_TICK || MODE == MODE_TRANSITION) init_word = v.init[slot];
       if (MODE == MODE_TICK || MODE == MODE_LANG) {
-        if (a.actions) act = a.actions[slot];
+        if constexpr (kHead) lrow = load_logit_row(a.logits, slot);
+        else if (a.actions) act = a.actions[slot];
         // (MODE_LANG: use_alt and alt_actions, the same two loads in the same batch)
         if (a.bc) {
           bc = a.bc[slot];
@@ -185,7 +196,8 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
         }
       } else {
         if (kTick) {
-          if (!a.actions) act = hashed_action(v, a.seed, slot, a.tick);
+          if constexpr (kHead) act = policy_head(lrow, a.head_mode, a.head_seed, (uint64_t)(v.env_base + slot), a.tick);
+          else if (!a.actions) act = hashed_action(v, a.seed, slot, a.tick);
           asm volatile("" : "+v"(bc), "+v"(ref));                      // (no early wait on the flag)
           // behaviour cloning, imitation.py:56-57; MODE_LANG: the ASK bit's candidate action,
           // active_primitive_language.py:59-61

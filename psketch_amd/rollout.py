@@ -69,7 +69,8 @@ class RolloutInfo(_Info):
 
 
 def do_rollout(sim, spec, act, is_eval, behavior_clone=None, receive=None, keep_obs=False,
-               timing=None, fused_teacher=True, lookahead=False, graph=0, graph_key=None):
+               timing=None, fused_teacher=True, lookahead=False, graph=0, graph_key=None, head=None,
+               head_seed=0):
     """One rollout of sim.n_envs episodes.
 
     spec: (scenario, x, y, dir, task), each n_envs ints (device or host).
@@ -105,6 +106,11 @@ def do_rollout(sim, spec, act, is_eval, behavior_clone=None, receive=None, keep_
       no-ops and are discarded.  The rollout's buffers are the simulator's own: the results are
       copies, and receive() is called once per real tick after the loop, in tick order, with
       rows of a copy of the labels.  Not with keep_obs.
+    head: None, "argmax" or "sample".  With a head, act(obs, t) returns the student's float32
+      [n, 6] logits instead of actions and the tick chooses each env's action itself
+      (craft_step_policy: the first maximum, or a draw from the softmax keyed by head_seed, the
+      env's global id and t), so no argmax / Categorical.sample kernels and no [n] round trip run
+      between the student's last GEMM and the step.  Works with graph and lookahead alike.
     graph_key: a hashable naming what the captured graphs read besides the simulator (the
       student's state); the graphs are reused only while act is the same callable and the key is
       equal, and captured anew otherwise.  A student that re-allocates a tensor act reads (a
@@ -114,7 +120,7 @@ def do_rollout(sim, spec, act, is_eval, behavior_clone=None, receive=None, keep_
     """
     if graph:
         return _graph_rollout(sim, spec, act, is_eval, behavior_clone, receive, keep_obs, timing,
-                              fused_teacher, int(graph), graph_key)
+                              fused_teacher, int(graph), graph_key, head, head_seed)
     t_start = time.perf_counter()
     n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
     if T <= 0:
@@ -154,14 +160,14 @@ def do_rollout(sim, spec, act, is_eval, behavior_clone=None, receive=None, keep_
             sim.teacher(action_out=refs[t])      # done (frozen) envs get -1
         labels_ready.record(side)
 
-    step = _stepper(sim, fused, bc, success)
+    step = _stepper(sim, fused, bc, success, head, head_seed)
     cur = {"obs": obs}
 
     def issue(t):
         """Tick t on the stream: the student's act, then one step launch (behaviour cloning, the
         action record, the any-live flag and, fused, the next tick's labels), then the flag's
         event (after the flag's copy to the host where it is not mapped)."""
-        actions = _actions(act(cur["obs"], t), n, dev)
+        actions = _policy_output(act(cur["obs"], t), n, dev, head)
         if side is not None:
             main.wait_event(labels_ready)
         if keep_obs:
@@ -201,10 +207,13 @@ def do_rollout(sim, spec, act, is_eval, behavior_clone=None, receive=None, keep_
                    t_loop, t_end_loop, dev)
 
 
-def _stepper(sim, teach, bc, success):
+def _stepper(sim, teach, bc, success, head=None, head_seed=0):
     """do_rollout's per-tick craft_step_ex / craft_step_teach (include/craft.h) with the argument
     struct built once: a tick sets only its pointers and the tick number (every buffer is one
-    do_rollout allocated and shaped itself, or the student's int32 [n] actions)."""
+    do_rollout allocated and shaped itself, or the student's int32 [n] actions).  With a head the
+    student's output is its float32 [n, 6] logits and the call is craft_step_policy."""
+    if head is not None:
+        return _policy_stepper(sim, teach, bc, success, head, head_seed)
     args = N.craft_step_args_t()
     args.flags = 0                                         # no auto-reset: done envs freeze
     if bc is not None:
@@ -228,6 +237,41 @@ def _stepper(sim, teach, bc, success):
     return step
 
 
+def _head_struct(head, head_seed):
+    if head not in N.HEAD_MODES:
+        raise ValueError(f"head must be None, 'argmax' or 'sample', got {head!r}")
+    hd = N.craft_policy_head_t()
+    hd.mode = N.HEAD_MODES[head]
+    hd.seed = int(head_seed) & (2**64 - 1)
+    return hd
+
+
+def _policy_stepper(sim, teach, bc, success, head, head_seed):
+    """_stepper's twin for do_rollout(head=...): craft_step_policy, label_out set when `teach`."""
+    args = N.craft_step_args_t()
+    args.flags = 0
+    if bc is not None:
+        args.behavior_clone = bc.data_ptr()
+    args.success = success.data_ptr()
+    hd = _head_struct(head, head_seed)
+    lib = sim._L
+    fn = lib.craft_step_policy
+    h, pargs, phead, di = sim._h, ctypes.byref(args), ctypes.byref(hd), sim.device.index
+    raw = (lambda _: None) if sim._cpu else torch._C._cuda_getCurrentRawStream
+
+    def step(t, logits, obs, ref, rec, live_ptr, labels):
+        hd.logits = logits.data_ptr()
+        args.tick = t
+        args.obs = obs.data_ptr()
+        args.ref_actions = None if ref is None else ref.data_ptr()
+        args.action_record = rec.data_ptr()
+        args.any_live = live_ptr
+        st = fn(h, pargs, phead, labels.data_ptr() if teach else None, raw(di))
+        if st:
+            N.check(st, h, "craft_step_policy", L=lib)
+    return step
+
+
 def _bc_mask(behavior_clone, n, dev):
     if behavior_clone is None:
         raise ValueError("behavior_clone is required when not is_eval")
@@ -245,7 +289,7 @@ def drop_graphs(sim):
 
 
 def _graph_rollout(sim, spec, act, is_eval, behavior_clone, receive, keep_obs, timing,
-                   fused_teacher, G, graph_key=None):
+                   fused_teacher, G, graph_key=None, head=None, head_seed=0):
     """do_rollout(graph=G): see do_rollout."""
     t_start = time.perf_counter()
     n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
@@ -263,7 +307,7 @@ def _graph_rollout(sim, spec, act, is_eval, behavior_clone, receive, keep_obs, t
     flags, events = live.host, live.events       # one event per chunk, read flag by flag
     gs = getattr(sim, "_graph_state", None)
     side_teacher = not is_eval and not fused_teacher
-    key = (is_eval, G, T, graph_key, side_teacher)
+    key = (is_eval, G, T, graph_key, side_teacher, head, head_seed)
     if gs is None or not _same_act(gs["act"], act) or gs["key"] != key:
         sim._graph_state = None                  # drop the old graphs before capturing new ones
         gs = sim._graph_state = {
@@ -282,7 +326,7 @@ def _graph_rollout(sim, spec, act, is_eval, behavior_clone, receive, keep_obs, t
         sim.teacher(action_out=refs[0])          # the initial states' labels; then every step's
     nch = (T + G - 1) // G
     if not gs["graphs"]:
-        step = _stepper(sim, not is_eval and not side_teacher, gs["bc"], success)
+        step = _stepper(sim, not is_eval and not side_teacher, gs["bc"], success, head, head_seed)
         main = torch.cuda.current_stream(dev)
         side = _teacher_stream(sim) if side_teacher else None
 
@@ -295,7 +339,7 @@ def _graph_rollout(sim, spec, act, is_eval, behavior_clone, receive, keep_obs, t
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
                     sim.teacher(action_out=refs[t])
-            actions = _actions(act(obs, t), n, dev)
+            actions = _policy_output(act(obs, t), n, dev, head)
             if side is not None and t > 0:
                 cur.wait_stream(side)
             step(t, actions, obs, None if is_eval else refs[t], seqs[t], live.ptr(t),
@@ -372,6 +416,16 @@ def _actions(a, n, dev):
     if not torch.is_tensor(a):
         a = torch.as_tensor(np.asarray(a), device=dev)
     return a.to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+
+
+def _policy_output(a, n, dev, head):
+    """What the student's act returned, as the step takes it: int32 [n] actions, or with a head
+    its float32 [n, 6] logits (a tensor on the simulator's device; made contiguous float32)."""
+    if head is None:
+        return _actions(a, n, dev)
+    if not torch.is_tensor(a) or a.device != dev or tuple(a.shape) != (n, N.N_ACTIONS):
+        raise ValueError(f"with head={head!r} act must return a [{n}, {N.N_ACTIONS}] logits tensor on {dev}")
+    return a.to(torch.float32).contiguous()
 
 
 def _teacher_stream(sim):
@@ -559,7 +613,7 @@ def _cut_episodes(ended, pose, succ, count, rec=None, T=None):
     return length, success, end_pose, seqs
 
 
-def evaluate(sim, specs, act, ids=None, max_ticks=None):
+def evaluate(sim, specs, act, ids=None, max_ticks=None, head=None, head_seed=0):
     """One pass over `specs` (ImitationTrainer.evaluate, trainers/imitation.py:183-226): every
     instance is run once, in eval mode, and a slot that finishes one moves straight on to the
     next (the episode queue, craft_step_stream) instead of idling until its batch is done.
@@ -572,15 +626,17 @@ def evaluate(sim, specs, act, ids=None, max_ticks=None):
       timing.  The action of an idle slot is ignored (any value in 0..5).
     max_ticks: a bound on the pass (default: ceil(count / n) * max_timesteps, which it cannot
       exceed); RuntimeError if it ends with slots still running.
+    head: None, "argmax" or "sample": as do_rollout's, act returns float32 [n, 6] logits and the
+      tick chooses the action (craft_step_policy_stream).
     The failed get episodes' distances (imitation.py:83-91: find_closest_resources on the
     initial grid at the final pose) are computed after the pass from the queue entries and the
     recorded final poses (craft_episode_summary): the simulator's slots are left as the pass
     left them.
     Raises RolloutError where the reference raises (success None; no reachable target)."""
-    return _queue_pass(sim, specs, act, ids, max_ticks, lang=False)
+    return _queue_pass(sim, specs, act, ids, max_ticks, lang=False, head=head, head_seed=head_seed)
 
 
-def _queue_pass(sim, specs, act, ids, max_ticks, lang):
+def _queue_pass(sim, specs, act, ids, max_ticks, lang, head=None, head_seed=0):
     """evaluate()'s pass over the queue under either protocol: craft_step_stream (the imitation
     trainer's), or with `lang` craft_step_lang_stream (the language trainers':
     language_rollout.evaluate).  The two argument structs name their shared fields alike."""
@@ -602,6 +658,11 @@ def _queue_pass(sim, specs, act, ids, max_ticks, lang):
     ctx = EvalContext(torch.arange(n, **i32), torch.zeros(n, **i32), torch.ones(n, **i32))
     live = _LiveFlags(sim, max_ticks)
     what = "craft_step_lang_stream" if lang else "craft_step_stream"
+    hd = None
+    if head is not None:
+        if lang:
+            raise ValueError("the language ticks take no policy head")
+        what, hd = "craft_step_policy_stream", _head_struct(head, head_seed)
     args = N.craft_lang_stream_step_args_t() if lang else N.craft_stream_step_args_t()
     args.step.flags = 0 if lang else N.STEP_AUTORESET
     args.step.obs = obs.data_ptr()
@@ -610,15 +671,18 @@ def _queue_pass(sim, specs, act, ids, max_ticks, lang):
     t = 0
     running = True
     while running and t < max_ticks:
-        actions = _actions(act(obs, ctx), n, dev)
-        args.step.actions = actions.data_ptr()
+        actions = _policy_output(act(obs, ctx), n, dev, head)
+        if hd is None:
+            args.step.actions = actions.data_ptr()
+        else:
+            hd.logits = actions.data_ptr()
         args.step.tick = t
         args.step.success = succ[t].data_ptr()
         args.step.action_record = rec[t].data_ptr()
         args.step.any_live = live.ptr(t)
         args.episode_end = ended[t].data_ptr()
         args.end_pose = pose[t].data_ptr()
-        st = fn(h, pargs, sim._stream())
+        st = fn(h, pargs, sim._stream()) if hd is None else fn(h, pargs, ctypes.byref(hd), sim._stream())
         if st:
             N.check(st, h, what, L=sim._L)
         # the next call's context, on the device
@@ -958,7 +1022,7 @@ class ImitationRollout:
             self._sims[n] = s
         return s
 
-    def do_rollout(self, batch, act, is_eval, receive=None, keep_obs=False):
+    def do_rollout(self, batch, act, is_eval, receive=None, keep_obs=False, head=None, head_seed=0):
         from .dataset import Dataset
         sim = self.sim(len(batch))
         spec = Dataset.specs(batch)
@@ -966,12 +1030,13 @@ class ImitationRollout:
         if not is_eval:
             bc = self.random.binomial(1, self.policy_mix_rate, size=len(batch))
         return do_rollout(sim, spec, act, is_eval, behavior_clone=bc, receive=receive,
-                          keep_obs=keep_obs)
+                          keep_obs=keep_obs, head=head, head_seed=head_seed)
 
-    def evaluate(self, dataset, act, n_envs=32):
+    def evaluate(self, dataset, act, n_envs=32, head=None, head_seed=0):
         """ImitationTrainer.evaluate(dataset, ...) (trainers/imitation.py:183-226): one pass
         over every instance of `dataset` (a Dataset, or any sequence of its items) on a
         simulator of n_envs slots; see evaluate().  Returns an EvalInfo."""
         from .dataset import Dataset
         items = list(dataset)
-        return evaluate(self.sim(n_envs), Dataset.specs(items), act, ids=[it["id"] for it in items])
+        return evaluate(self.sim(n_envs), Dataset.specs(items), act, ids=[it["id"] for it in items],
+                        head=head, head_seed=head_seed)

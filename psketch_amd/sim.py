@@ -387,10 +387,41 @@ class CraftSim:
                     "craft_reset")
         return obs
 
+    def _head(self, keep, logits, head, head_seed):
+        """The craft_policy_head_t of a float32 [N, 6] logits tensor; head: "argmax", "sample" or
+        a CRAFT_HEAD_* value (the library refuses any other)."""
+        self._buf("logits", logits, torch.float32, (self.n_envs, N.N_ACTIONS))
+        hd = N.craft_policy_head_t()
+        _put(hd, keep, "logits", logits)
+        if isinstance(head, str):
+            if head not in N.HEAD_MODES:
+                raise ValueError(f"head must be 'argmax' or 'sample', got {head!r}")
+            head = N.HEAD_MODES[head]
+        hd.mode = int(head)
+        hd.seed = int(head_seed) & (2**64 - 1)
+        return hd
+
+    def policy_actions(self, logits, mode="argmax", seed=0, tick=0, out=None):
+        """The policy head alone (craft_policy_actions): int32 [N] actions of float32 [N, 6]
+        logits, -1 for a row with a NaN or +inf or nothing but -inf.  mode "argmax": the first
+        maximum; "sample": a draw from the softmax keyed by (seed, global env id, tick), the
+        same on every device and for every sharding."""
+        if out is None:
+            out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        self._buf("out", out, torch.int32, (self.n_envs,))
+        keep = []
+        hd = self._head(keep, logits, mode, seed)
+        self._check(self._L.craft_policy_actions(self._h, ctypes.byref(hd), int(tick), _ptr(out), self._stream()),
+                    "craft_policy_actions")
+        return out
+
     def step(self, actions=None, seed=0, tick=0, autoreset=True, obs=None, reward=None, done=None,
              success=None, ref_actions=None, behavior_clone=None, action_record=None,
-             any_live=None, transition_code=None, labels=None):
+             any_live=None, transition_code=None, labels=None, logits=None, head="argmax", head_seed=0):
         """One rollout tick for every slot (include/craft.h craft_step / craft_step_ex).
+        logits (float32 [N, 6]) in place of actions: the tick chooses each slot's action itself
+        (craft_step_policy), head = "argmax" (the first maximum) or "sample" (a draw from the
+        softmax keyed by head_seed, the global env id and tick).
         actions: int32 device tensor [N] or None for the in-kernel hashed draw;
         ref_actions + behavior_clone (uint8 [N]): cloned actions; action_record
         (int32 [N]) receives the action taken (-1 for done slots); any_live (a
@@ -400,7 +431,7 @@ class CraftSim:
         would return right after this step."""
         n = self.n_envs
         flags = N.STEP_AUTORESET if autoreset else 0
-        if ref_actions is None and behavior_clone is None and action_record is None \
+        if logits is None and ref_actions is None and behavior_clone is None and action_record is None \
                 and any_live is None and transition_code is None and labels is None:
             # plain tick: the short craft_step entry (least host overhead per launch)
             a = self._i32(actions, n) if actions is not None else None
@@ -418,7 +449,12 @@ class CraftSim:
         args.action_seed = seed & (2**64 - 1)
         args.tick = int(tick)
         args.flags = flags
-        if labels is not None:
+        if logits is not None:
+            self._buf("labels", labels, torch.int32, (n,))
+            hd = self._head(keep, logits, head, head_seed)
+            self._check(self._L.craft_step_policy(self._h, ctypes.byref(args), ctypes.byref(hd), _ptr(labels),
+                                                  self._stream()), "craft_step_policy")
+        elif labels is not None:
             self._buf("labels", labels, torch.int32, (n,))
             self._check(self._L.craft_step_teach(self._h, ctypes.byref(args), _ptr(labels),
                                                  self._stream()), "craft_step_teach")
@@ -477,9 +513,9 @@ class CraftSim:
     def step_stream(self, actions=None, seed=0, tick=0, obs=None, reward=None, done=None,
                     success=None, ref_actions=None, behavior_clone=None, action_record=None,
                     any_live=None, transition_code=None, labels=None, episode_end=None,
-                    end_pose=None, episode_now=None):
+                    end_pose=None, episode_now=None, logits=None, head="argmax", head_seed=0):
         """step(autoreset=True) whose restart takes the slot's next queue entry
-        (craft_step_stream), with three more int32 [N] outputs: episode_end (the queue index of
+        (craft_step_stream; with logits in place of actions craft_step_policy_stream, as step), with three more int32 [N] outputs: episode_end (the queue index of
         the episode that ended this tick, else -1), end_pose (x | y << 8 | dir << 16 of its
         final state, else -1) and episode_now (the queue index the slot runs after the tick, -1
         once it has run out).  any_live: some slot is still running after the tick."""
@@ -494,6 +530,11 @@ class CraftSim:
         st.flags = N.STEP_AUTORESET
         self._put_bufs(args, keep, (("label_out", labels, torch.int32, (n,)),))
         self._queue_outs(args, keep, (n,), episode_end, end_pose, episode_now)
+        if logits is not None:
+            hd = self._head(keep, logits, head, head_seed)
+            self._check(self._L.craft_step_policy_stream(self._h, ctypes.byref(args), ctypes.byref(hd),
+                                                         self._stream()), "craft_step_policy_stream")
+            return obs
         self._check(self._L.craft_step_stream(self._h, ctypes.byref(args), self._stream()),
                     "craft_step_stream")
         return obs

@@ -8,6 +8,12 @@ gaps between them count:
   both     policy then step per tick, 40 ticks (one do_rollout's device work)
   side_teacher   craft_teacher on a side stream beside the policy, then craft_step_ex
   graph    `both` captured as one HIP graph and replayed
+  head_argmax   addmm, then craft_step_policy (the tick chooses the first maximum itself) with the
+                teacher: `both` without the argmax and cast kernels and their [n] round trip
+  torch_sample  addmm + Categorical(logits).sample() + cast + craft_step_teach: the training loop
+  head_sample   addmm, then craft_step_policy drawing from the softmax in the tick
+  head_split    addmm, craft_policy_actions, craft_step_teach: the head as a launch of its own
+                (each of the four also as a graph: <name>_graph)
 
     python tools/loop_probe.py [--envs 65536] [--reps 5]
 """
@@ -35,7 +41,24 @@ def main():
     sim.load_pool(grids)
     tasks = [t.id for t in sim.task_manager.dataset_tasks()]
     specs = synthetic_specs(grids, 12, 12, n, 0, seed=0, task_ids=tasks)
-    act, _, _ = bench.trainer_policy(sim.n_features, sim.device)
+    act, W, bias = bench.trainer_policy(sim.n_features, sim.device)
+    Wd = torch.as_tensor(W, dtype=torch.float32, device=sim.device)
+    bd = torch.as_tensor(bias, dtype=torch.float32, device=sim.device)
+    head_acts = torch.empty(n, dtype=torch.int32, device=sim.device)
+
+    def logits(t):                                        # the student up to its last GEMM
+        return torch.addmm(bd, obs, Wd[t % Wd.shape[0]], alpha=8)
+
+    def head_tick(t, mode):
+        sim.step(logits=logits(t), head=mode, head_seed=11, tick=t, autoreset=True, obs=obs, labels=labels[t + 1])
+
+    def torch_sample_tick(t):
+        a = torch.distributions.Categorical(logits=logits(t), validate_args=False).sample().to(torch.int32)
+        sim.step(a, tick=t, autoreset=True, obs=obs, labels=labels[t + 1])
+
+    def head_split_tick(t):
+        sim.policy_actions(logits(t), "argmax", tick=t, out=head_acts)
+        sim.step(head_acts, tick=t, autoreset=True, obs=obs, labels=labels[t + 1])
     obs = sim.empty_obs()
     labels = torch.empty((T + 1, n), dtype=torch.int32, device=sim.device)
     acts = torch.randint(0, 5, (n,), dtype=torch.int32, device=sim.device)
@@ -70,6 +93,10 @@ def main():
         "teacher": lambda: [sim.teacher(action_out=labels[t]) for t in range(T)],
         "both": lambda: [step(t, policy(t)) for t in range(T)],
         "side_teacher": lambda: [side_tick(t) for t in range(T)],
+        "head_argmax": lambda: [head_tick(t, "argmax") for t in range(T)],
+        "torch_sample": lambda: [torch_sample_tick(t) for t in range(T)],
+        "head_sample": lambda: [head_tick(t, "sample") for t in range(T)],
+        "head_split": lambda: [head_split_tick(t) for t in range(T)],
     }
     sim.reset(*specs)
     for f in seqs.values():
@@ -81,6 +108,12 @@ def main():
     with torch.cuda.graph(g):
         seqs["both"]()
     seqs["graph"] = g.replay
+    for name in ("head_argmax", "torch_sample", "head_sample", "head_split"):
+        gh = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.cuda.graph(gh):
+            seqs[name]()
+        seqs[name + "_graph"] = gh.replay
     out = {"envs": n, "ticks": T}
     for name, f in seqs.items():
         us = []
