@@ -578,6 +578,63 @@ int craft_step_policy(craft_sim_t* sim, const craft_step_args_t* step, const cra
 int craft_step_policy_stream(craft_sim_t* sim, const craft_stream_step_args_t* args,
                              const craft_policy_head_t* head, void* stream);
 
+/* ---- the policy head on the language tick ------------------------------------------------------
+ * The three language students decide as the imitation student does (students/
+ * active_primitive_language.py:113-131, instructed_act :139-143), and the active student also asks
+ * the teacher wherever entropy(softmax(l)) / ln 6 > threshold (:116-119).  In the reference the
+ * instructed model's logits depend on the ask bits (an asking env's instruction is replaced before
+ * instructed_act runs, trainers/active_primitive_language.py:51-57), so the order of a tick is:
+ * the main model decodes; the ask bits; the instructions; the instructed model decodes; the tick.
+ * craft_policy_ask is the second step as one launch; the tick takes both logit tensors and the bits.
+ *
+ * The ask rule.  The row l[0..5] and the arithmetic are the head rule's (binary32, round to nearest
+ * even, no contraction other than the fmaf written here).  No logarithm: H = ln S - A / S > T is
+ * decided as S > e^(T + A / S), with craft_expf on the side that keeps its argument in [-80, 0].
+ *   1. bad and m as in step 1 of the head rule.  If bad, or m == -inf, ask = 0 and nothing below runs
+ *      (the reference's NaN entropy compares false as well).
+ *   2. For k = 0..5 in order: dk = max(l[k] - m, -80.0f); w[k] = 0 when l[k] == -inf, else
+ *      craft_expf(dk); S = w[0], then S = S + w[k]  (S is c[5] of the head rule; craft_expf(0) is
+ *      exactly 1, so S >= 1); A = 0, then A = fmaf(w[k], dk, A), skipped where l[k] == -inf
+ *      (A <= 0; the entropy is ln S - A / S).
+ *   3. T = threshold * LN6, LN6 = 1.79175949f (0x3FE55860, the float nearest ln 6), a rounded product;
+ *      q = A / S, the correctly rounded IEEE division; x = T + q, a rounded sum (never fused with
+ *      the product).
+ *   4. If !(x > 0): ask = S > craft_expf(max(x, -80.0f)).
+ *      Otherwise:   ask = S * craft_expf(-x) > 1.0f    (x <= ln 6: the argument is within range).
+ * Against the float64 definition the three compared quantities each carry under 1e-6 absolute
+ * (craft_expf's 2^-21 relative, six-term sums), so the bit can differ only where the normalised
+ * entropy is within 2.5e-6 of the threshold (DESIGN.md has the measured figure).
+ *
+ * ask_out (device uint8[n_envs]) = the ask bit of every slot's row of head->logits; head->mode and
+ * head->seed are not read.  One small launch, like craft_policy_actions.  CRAFT_EINVAL: a NULL
+ * head or head->logits, a logits base that is not 8-byte aligned, a NULL ask_out, a threshold that
+ * is NaN or outside [0, 1]. */
+int craft_policy_ask(craft_sim_t* sim, const craft_policy_head_t* head, float threshold,
+                     uint8_t* ask_out, void* stream);
+
+/* craft_step_lang with actions[i] = head(i) at args->tick and, with alt_head, alt_actions[i] =
+ * alt_head(i), in the same single launch: the slot acts on use_alt[i] ? alt_head(i) : head(i).
+ * Each head has its own mode and seed (two SAMPLE heads given one seed would draw from the same
+ * uniform number: seed them apart).  The kernel requests both rows and the use_alt byte beside the
+ * slot's state, selects row, mode and seed per slot and runs the head once on the selection.
+ * With alt_head NULL, alt_actions / use_alt may still be given as integers exactly as under
+ * craft_step_lang (the interactive trainer, where every env follows the instructed model, is
+ * simply head = the instructed logits).  Every output, the slot state, the statistics and the
+ * latched error are those of craft_policy_actions on each head followed by craft_step_lang on the
+ * two vectors: only the selected head's -1 can latch CRAFT_EBADACTION, a bad main row on a slot
+ * that takes its alt action is harmless, as an integer actions[i] = -1 is there.
+ * CRAFT_EINVAL (the message names the reason): the head's refusals, for head and then for
+ * alt_head; args->actions != NULL; alt_head together with alt_actions != NULL; alt_head without
+ * use_alt; then everything craft_step_lang refuses, with its message. */
+int craft_step_lang_policy(craft_sim_t* sim, const craft_lang_step_args_t* args,
+                           const craft_policy_head_t* head, const craft_policy_head_t* alt_head,
+                           void* stream);
+
+/* craft_step_lang_stream likewise (args->step is the craft_lang_step_args_t the rules above read). */
+int craft_step_lang_policy_stream(craft_sim_t* sim, const craft_lang_stream_step_args_t* args,
+                                  const craft_policy_head_t* head, const craft_policy_head_t* alt_head,
+                                  void* stream);
+
 /* n_ticks consecutive craft_step ticks (tick0, tick0+1, ...) in one launch, with
  * results identical to n_ticks craft_step calls: each workgroup keeps its envs
  * on chip between ticks, so the per-tick prologue overlaps other workgroups'

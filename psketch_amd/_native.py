@@ -266,6 +266,12 @@ SIGNATURES = {
     "craft_step_policy_stream": (_i32, [_vp, ctypes.POINTER(craft_stream_step_args_t),
                                         ctypes.POINTER(craft_policy_head_t), _vp]),
     "craft_step_lang": (_i32, [_vp, ctypes.POINTER(craft_lang_step_args_t), _vp]),
+    "craft_policy_ask": (_i32, [_vp, ctypes.POINTER(craft_policy_head_t), ctypes.c_float, _vp, _vp]),
+    "craft_step_lang_policy": (_i32, [_vp, ctypes.POINTER(craft_lang_step_args_t), ctypes.POINTER(craft_policy_head_t),
+                                      ctypes.POINTER(craft_policy_head_t), _vp]),
+    "craft_step_lang_policy_stream": (_i32, [_vp, ctypes.POINTER(craft_lang_stream_step_args_t),
+                                             ctypes.POINTER(craft_policy_head_t),
+                                             ctypes.POINTER(craft_policy_head_t), _vp]),
     "craft_episode_queue": (_i32, [_vp, _vp, _i64]),
     "craft_episode_begin": (_i32, [_vp, _i64, _i64, _u32, _vp, _vp]),
     "craft_step_stream": (_i32, [_vp, ctypes.POINTER(craft_stream_step_args_t), _vp]),

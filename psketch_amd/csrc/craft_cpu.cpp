@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "craft_checks_episode_summary.h"
+#include "craft_checks_lang_policy.h"
 #include "craft_checks_lang_stream.h"
 #include "craft_checks_policy.h"
 #include "craft_checks_rollout_replay.h"
@@ -565,6 +566,34 @@ void policy_actions(craft_sim* s, const craft_policy_head_t* h, int64_t tick, in
     for (int64_t i = lo; i < hi; ++i)
       out[i] = policy_head(h->logits + 6 * i, h->mode, h->seed, (uint64_t)(s->env_base + i), tick);
   });
+}
+
+// The ask rule (include/craft.h "The ask rule"), this library's own copy likewise.  T + q is a
+// product feeding a sum: T is volatile, so a compiler with a fused multiply-add still rounds it
+// first and keeps the two roundings the rule has (`/` is IEEE's: no fast-math here).
+int policy_ask(const float* l, float threshold) {
+  const float inf = std::numeric_limits<float>::infinity();
+  bool bad = !(l[0] < inf);
+  float m = l[0];
+  for (int k = 1; k < 6; ++k) {
+    bad = bad || !(l[k] < inf);
+    m = (l[k] > m) ? l[k] : m;
+  }
+  if (bad || m == -inf) return 0;
+  float S = 0.0f, A = 0.0f;
+  for (int k = 0; k < 6; ++k) {
+    const float d = l[k] - m;
+    const float dk = d > -80.0f ? d : -80.0f;
+    const bool masked = l[k] == -inf;
+    const float w = masked ? 0.0f : craft_expf(dk);
+    S = k == 0 ? w : S + w;
+    if (!masked) A = std::fmaf(w, dk, A);
+  }
+  volatile float T = threshold * bits_float(0x3FE55860u);   // ln 6
+  const float q = A / S;
+  const float x = T + q;
+  if (!(x > 0.0f)) return S > craft_expf(x > -80.0f ? x : -80.0f) ? 1 : 0;
+  return S * craft_expf(-x) > 1.0f ? 1 : 0;
 }
 
 // A slot reset / set_state has initialised: an interior position on a loaded pool row.
@@ -1117,6 +1146,42 @@ int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* /*str
   return CRAFT_OK;
 }
 
+int craft_policy_ask(craft_sim_t* s, const craft_policy_head_t* head, float threshold, uint8_t* ask_out,
+                     void* /*stream*/) {
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_policy_ask(head, threshold, ask_out, s->last_error)) return rc;
+  parallel_for(s, s->n_envs, [&](int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i) ask_out[i] = (uint8_t)policy_ask(head->logits + 6 * i, threshold);
+  });
+  return CRAFT_OK;
+}
+
+// The language ticks on the heads' actions: both heads run as passes of their own over every slot
+// (this library is the implementation the fused kernels are checked against), then the wrapped
+// entry point takes the two vectors.
+struct LangHeadActions {
+  std::vector<int32_t> main, alt;
+  LangHeadActions(craft_sim* s, const craft_policy_head_t* head, const craft_policy_head_t* alt_head, int64_t tick,
+                  craft_lang_step_args_t& y)
+      : main((size_t)s->n_envs), alt(alt_head ? (size_t)s->n_envs : 0) {
+    policy_actions(s, head, tick, main.data());
+    y.actions = main.data();
+    if (alt_head) {
+      policy_actions(s, alt_head, tick, alt.data());
+      y.alt_actions = alt.data();
+    }
+  }
+};
+
+int craft_step_lang_policy(craft_sim_t* s, const craft_lang_step_args_t* x, const craft_policy_head_t* head,
+                           const craft_policy_head_t* alt_head, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_step_lang_policy(facts(s), x, head, alt_head, s->last_error)) return rc;
+  craft_lang_step_args_t y = *x;
+  const LangHeadActions acts(s, head, alt_head, x->tick, y);
+  return craft_step_lang(s, &y, stream);
+}
+
 // ---- the episode queue ------------------------------------------------------------------------
 // Written out on its own (no call into tick_slot): this library is the second implementation
 // the HIP kernels are checked against.
@@ -1367,6 +1432,16 @@ int craft_step_lang_stream(craft_sim_t* s, const craft_lang_stream_step_args_t* 
   });
   tot.commit(s, p.any_live);
   return CRAFT_OK;
+}
+
+int craft_step_lang_policy_stream(craft_sim_t* s, const craft_lang_stream_step_args_t* x,
+                                  const craft_policy_head_t* head, const craft_policy_head_t* alt_head,
+                                  void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_step_lang_policy_stream(facts(s), x, head, alt_head, s->last_error)) return rc;
+  craft_lang_stream_step_args_t y = *x;
+  const LangHeadActions acts(s, head, alt_head, x->step.tick, y.step);
+  return craft_step_lang_stream(s, &y, stream);
 }
 
 int craft_rollout(craft_sim_t* s, const int32_t* actions, uint64_t action_seed, int64_t tick0, int32_t n_ticks,

@@ -35,11 +35,20 @@ constexpr int kInvStride = 36;     // LDS bytes per inventory row (9 dwords: ban
 // MODE_LANG_STREAM: MODE_LANG on the episode queue: the ending tick steps, then the slot restarts (craft_step_lang_stream)
 // MODE_TICK_HEAD, MODE_STREAM_HEAD: MODE_TICK / MODE_STREAM whose action is the policy head's (craft_step_policy,
 // craft_step_policy_stream; craft_policy.h): instantiations of their own, the two base modes' code is untouched
+// MODE_LANG_HEAD, MODE_LANG_STREAM_HEAD: MODE_LANG / MODE_LANG_STREAM likewise (craft_step_lang_policy,
+// craft_step_lang_policy_stream): the head of the main row or, per slot by use_alt, of the alt row
 enum Mode { MODE_TICK = 0, MODE_TRANSITION = 1, MODE_OBSERVE = 2, MODE_RESET = 3, MODE_LANG = 4, MODE_STREAM = 5,
-            MODE_LANG_STREAM = 6, MODE_TICK_HEAD = 7, MODE_STREAM_HEAD = 8 };
-__host__ __device__ constexpr bool mode_has_head(int mode) { return mode == MODE_TICK_HEAD || mode == MODE_STREAM_HEAD; }
+            MODE_LANG_STREAM = 6, MODE_TICK_HEAD = 7, MODE_STREAM_HEAD = 8, MODE_LANG_HEAD = 9,
+            MODE_LANG_STREAM_HEAD = 10 };
+__host__ __device__ constexpr bool mode_has_head(int mode) {
+  return mode == MODE_TICK_HEAD || mode == MODE_STREAM_HEAD || mode == MODE_LANG_HEAD || mode == MODE_LANG_STREAM_HEAD;
+}
 __host__ __device__ constexpr int mode_base(int mode) {
-  return mode == MODE_TICK_HEAD ? (int)MODE_TICK : mode == MODE_STREAM_HEAD ? (int)MODE_STREAM : mode;
+  return mode == MODE_TICK_HEAD          ? (int)MODE_TICK
+         : mode == MODE_STREAM_HEAD      ? (int)MODE_STREAM
+         : mode == MODE_LANG_HEAD        ? (int)MODE_LANG
+         : mode == MODE_LANG_STREAM_HEAD ? (int)MODE_LANG_STREAM
+                                         : mode;
 }
 
 struct SimView {
@@ -266,6 +275,11 @@ struct TileArgs {
   const float* logits;
   uint64_t head_seed;
   int32_t head_mode;
+  // the language modes' second head (MODE_LANG_HEAD, MODE_LANG_STREAM_HEAD): the instructed model's row, mode and
+  // seed, taken by the slots whose use_alt (bc) is set; alt_logits null = alt_actions (ref) are integers as before
+  int32_t alt_mode;
+  const float* alt_logits;
+  uint64_t alt_seed;
 };
 
 struct RolloutArgs {       // craft_rollout: n_ticks ticks in one launch

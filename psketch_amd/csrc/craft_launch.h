@@ -16,7 +16,7 @@ hipError_t launch_tick2(int tl, int nw, const SimView& v, const TileArgs& a, siz
 size_t tick2_lds_bytes(int tl, int nw, int GS, int F);
 // craft_tick_lang.hip, craft_tick_stream.hip: tl = 0 launches the bare tick
 hipError_t launch_tick_lang(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                            hipStream_t st);
+                            hipStream_t st, bool head = false);
 hipError_t launch_tick_stream(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
                               hipStream_t st, bool head = false);
 // craft_tick_policy.hip, craft_tick_policy_stream.hip: where the three launchers above (and launch_tile's
@@ -28,9 +28,16 @@ hipError_t launch_tick_stream_head(int tl, int nw, int win, int tile, const SimV
                                    size_t lds, hipStream_t st);
 hipError_t launch_policy_actions(const float* logits, int32_t mode, uint64_t seed, int64_t gid0, int64_t tick,
                                  int64_t n, int32_t* actions_out, hipStream_t st);
+hipError_t launch_policy_ask(const float* logits, float threshold, int64_t n, uint8_t* ask_out, hipStream_t st);
+// craft_tick_lang_policy.hip, craft_tick_lang_policy_stream.hip: the language ticks' head instantiations
+// (MODE_LANG_HEAD, MODE_LANG_STREAM_HEAD), found by launch_tick_lang / launch_tick_lang_stream with head set
+hipError_t launch_tick_lang_head(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
+                                 hipStream_t st);
+hipError_t launch_tick_lang_stream_head(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a,
+                                        size_t lds, hipStream_t st);
 // craft_tick_lang_stream.hip
 hipError_t launch_tick_lang_stream(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                                   hipStream_t st);
+                                   hipStream_t st, bool head = false);
 hipError_t launch_queue_pack(const SimView& v, const int32_t* specs, int64_t count, uint2* out,
                              unsigned long long* first_bad, hipStream_t st);
 hipError_t launch_queue_begin(const uint2* entries, int64_t count, int64_t first_gid, int wrap, int64_t n,

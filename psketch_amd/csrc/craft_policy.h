@@ -1,10 +1,12 @@
 // craft_policy.h — the policy head (include/craft.h "The head rule"): a slot's action chosen from
 // its six logits inside the tick, the first maximum (CRAFT_HEAD_ARGMAX) or a draw from the softmax
 // keyed by (seed, global env id, tick) (CRAFT_HEAD_SAMPLE).  One device function for the tile
-// kernel's MODE_TICK_HEAD / MODE_STREAM_HEAD, tick2_kernel's head instantiations and
-// craft_policy_actions' own small kernel.  craft_cpu.cpp keeps its own copy on purpose (craft_episode.h says why); the two
-// must agree bit for bit, so everything here is +, *, explicit fmaf, rintf, comparisons and
-// integer bit operations: nothing a compiler may contract or approximate differently.
+// kernel's MODE_TICK_HEAD / MODE_STREAM_HEAD / MODE_LANG_HEAD / MODE_LANG_STREAM_HEAD, tick2_kernel's
+// head instantiations and craft_policy_actions' own small kernel; and the ask rule ("The ask
+// rule": policy_ask, craft_policy_ask's kernel).  craft_cpu.cpp keeps its own copy on purpose
+// (craft_episode.h says why); the two must agree bit for bit, so everything here is +, *, explicit
+// fmaf, rintf, comparisons and integer bit operations (and, in the ask rule, one IEEE division):
+// nothing a compiler may contract or approximate differently.
 #pragma once
 #include "craft_device.h"
 
@@ -77,6 +79,39 @@ __device__ __forceinline__ int policy_head(const LogitRow& row, const int32_t& m
 #pragma unroll
   for (int k = 1; k < 6; ++k) last = (w[k] > 0.0f) ? k : last;     // the largest k with weight
   return act < 0 ? last : act;
+}
+
+// The ask rule (include/craft.h "The ask rule"): 1 where the entropy of softmax(row), over ln 6,
+// exceeds `threshold` (0 <= threshold <= 1), 0 otherwise and for a row the head calls bad.  No log:
+// H = ln S - A / S > T is decided as S > e^(T + A / S), with craft_expf on whichever side keeps its
+// argument in [-80, 0].  The division is IEEE's (__fdiv_rn), the one operation here a fast-math
+// build could approximate.
+__device__ __forceinline__ int policy_ask(const LogitRow& row, float threshold) {
+  const float l[6] = {row.a.x, row.a.y, row.b.x, row.b.y, row.c.x, row.c.y};
+  const float inf = __uint_as_float(0x7F800000u);
+  bool bad = !(l[0] < inf);
+  float m = l[0];
+#pragma unroll
+  for (int k = 1; k < 6; ++k) {
+    bad = bad || !(l[k] < inf);
+    m = (l[k] > m) ? l[k] : m;
+  }
+  if (bad || m == -inf) return 0;
+  float S = 0.0f, A = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const float d = l[k] - m;
+    const float dk = d > -80.0f ? d : -80.0f;
+    const bool masked = l[k] == -inf;
+    const float w = masked ? 0.0f : craft_expf(dk);
+    S = k == 0 ? w : S + w;
+    A = masked ? A : fmaf(w, dk, A);
+  }
+  // (a product feeding a sum: __fmul_rn / __fadd_rn keep the two roundings the rule has)
+  const float T = __fmul_rn(threshold, __uint_as_float(0x3FE55860u));      // ln 6
+  const float x = __fadd_rn(T, __fdiv_rn(A, S));
+  if (!(x > 0.0f)) return S > craft_expf(x > -80.0f ? x : -80.0f) ? 1 : 0;
+  return S * craft_expf(-x) > 1.0f ? 1 : 0;
 }
 
 }  // namespace craft

@@ -16,6 +16,7 @@
 
 #include "craft_device.h"
 #include "craft_checks_episode_summary.h"
+#include "craft_checks_lang_policy.h"
 #include "craft_checks_lang_stream.h"
 #include "craft_checks_policy.h"
 #include "craft_checks_rollout_replay.h"
@@ -611,6 +612,43 @@ int run_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, const cra
   return CRAFT_OK;
 }
 
+// The language ticks likewise, each shared with its craft_step_lang_policy* twin: `head` the
+// main row's head, `alt` the alt row's (null: alt_actions are integers, or there are none).
+void lang_head_args(const craft_policy_head_t* head, const craft_policy_head_t* alt, TileArgs& a) {
+  head_args(head, a);
+  if (!alt) return;
+  a.alt_logits = alt->logits;
+  a.alt_mode = alt->mode;
+  a.alt_seed = alt->seed;
+}
+
+int run_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, const craft_policy_head_t* head,
+                  const craft_policy_head_t* alt, void* stream, const char* what) {
+  TileArgs a = lang_args(s, *x);
+  lang_head_args(head, alt, a);
+  TickPlan p;
+  const int rc = tick_plan(s, x->label_out != nullptr, stream, what, p);
+  if (rc != CRAFT_OK) return rc;
+  const hipError_t e = craft::launch_tick_lang(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
+                                               reinterpret_cast<hipStream_t>(stream), head != nullptr);
+  if (e != hipSuccess) return hip_fail(s, e, (std::string(what) + " launch").c_str());
+  return CRAFT_OK;
+}
+
+int run_step_lang_stream(craft_sim_t* s, const craft_lang_stream_step_args_t* x, const craft_policy_head_t* head,
+                         const craft_policy_head_t* alt, void* stream, const char* what) {
+  TileArgs a = lang_args(s, x->step);
+  queue_args(s, *x, a);
+  lang_head_args(head, alt, a);
+  TickPlan p;
+  const int rc = tick_plan(s, x->step.label_out != nullptr, stream, what, p);
+  if (rc != CRAFT_OK) return rc;
+  const hipError_t e = craft::launch_tick_lang_stream(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
+                                                      reinterpret_cast<hipStream_t>(stream), head != nullptr);
+  if (e != hipSuccess) return hip_fail(s, e, (std::string(what) + " launch").c_str());
+  return CRAFT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1095,16 +1133,33 @@ int craft_step_policy_stream(craft_sim_t* s, const craft_stream_step_args_t* x, 
 
 int craft_step_lang(craft_sim_t* s, const craft_lang_step_args_t* x, void* stream) {
   if (!s || !x) return CRAFT_EINVAL;
-  int rc = craft_host::check_step_lang(facts(s), x, s->last_error);
-  if (rc != CRAFT_OK) return rc;
-  const TileArgs a = lang_args(s, *x);
-  TickPlan p;
-  rc = tick_plan(s, x->label_out != nullptr, stream, "craft_step_lang", p);
-  if (rc != CRAFT_OK) return rc;
-  const hipError_t e = craft::launch_tick_lang(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
-                                               reinterpret_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return hip_fail(s, e, "craft_step_lang launch");
+  if (const int rc = craft_host::check_step_lang(facts(s), x, s->last_error)) return rc;
+  return run_step_lang(s, x, nullptr, nullptr, stream, "craft_step_lang");
+}
+
+int craft_policy_ask(craft_sim_t* s, const craft_policy_head_t* head, float threshold, uint8_t* ask_out,
+                     void* stream) {
+  if (!s) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_policy_ask(head, threshold, ask_out, s->last_error)) return rc;
+  const hipError_t e =
+      craft::launch_policy_ask(head->logits, threshold, s->n_envs, ask_out, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(s, e, "craft_policy_ask launch");
   return CRAFT_OK;
+}
+
+int craft_step_lang_policy(craft_sim_t* s, const craft_lang_step_args_t* x, const craft_policy_head_t* head,
+                           const craft_policy_head_t* alt_head, void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_step_lang_policy(facts(s), x, head, alt_head, s->last_error)) return rc;
+  return run_step_lang(s, x, head, alt_head, stream, "craft_step_lang_policy");
+}
+
+int craft_step_lang_policy_stream(craft_sim_t* s, const craft_lang_stream_step_args_t* x,
+                                  const craft_policy_head_t* head, const craft_policy_head_t* alt_head,
+                                  void* stream) {
+  if (!s || !x) return CRAFT_EINVAL;
+  if (const int rc = craft_host::check_step_lang_policy_stream(facts(s), x, head, alt_head, s->last_error)) return rc;
+  return run_step_lang_stream(s, x, head, alt_head, stream, "craft_step_lang_policy_stream");
 }
 
 int craft_episode_queue(craft_sim_t* s, const int32_t* specs, int64_t count) {
@@ -1185,17 +1240,8 @@ int craft_step_stream(craft_sim_t* s, const craft_stream_step_args_t* x, void* s
 
 int craft_step_lang_stream(craft_sim_t* s, const craft_lang_stream_step_args_t* x, void* stream) {
   if (!s || !x) return CRAFT_EINVAL;
-  int rc = craft_host::check_step_lang_stream(facts(s), x, s->last_error);
-  if (rc != CRAFT_OK) return rc;
-  TileArgs a = lang_args(s, x->step);
-  queue_args(s, *x, a);
-  TickPlan p;
-  rc = tick_plan(s, x->step.label_out != nullptr, stream, "craft_step_lang_stream", p);
-  if (rc != CRAFT_OK) return rc;
-  const hipError_t e = craft::launch_tick_lang_stream(p.tl, p.nw, s->cfg.window_width, p.tile, p.v, a, p.lds,
-                                                      reinterpret_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return hip_fail(s, e, "craft_step_lang_stream launch");
-  return CRAFT_OK;
+  if (const int rc = craft_host::check_step_lang_stream(facts(s), x, s->last_error)) return rc;
+  return run_step_lang_stream(s, x, nullptr, nullptr, stream, "craft_step_lang_stream");
 }
 
 int craft_step_ex(craft_sim_t* s, const craft_step_args_t* x, void* stream) {

@@ -11,8 +11,10 @@
 namespace craft {
 
 // tl = teacher lanes per env (1, 2 or 4), or 0: no teacher in the launch (tile 16, 32 or 64).
+// head: the policy head's instantiations (a.logits set; craft_tick_lang_policy.hip).
 hipError_t launch_tick_lang(int tl, int nw, int win, int tile, const SimView& v, const TileArgs& a, size_t lds,
-                            hipStream_t st) {
+                            hipStream_t st, bool head) {
+  if (head) return launch_tick_lang_head(tl, nw, win, tile, v, a, lds, st);
   if (tl == 0) return launch_tile_bare<MODE_LANG>(win, tile, v, a, lds, st);
   return launch_tile_teach<MODE_LANG>(tl, nw, win, tile, v, a, lds, st);
 }

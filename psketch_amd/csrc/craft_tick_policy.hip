@@ -1,5 +1,5 @@
 // craft_tick_policy.hip — the policy head (include/craft.h "The head rule", craft_policy.h):
-// craft_policy_actions' kernel, one thread per slot, and the tile kernel's MODE_TICK_HEAD
+// craft_policy_actions' and craft_policy_ask's kernels, one thread per slot, and the tile kernel's MODE_TICK_HEAD
 // instantiations that craft_step_policy launches (the shapes of craft_step_ex and of
 // craft_step_teach's one-tile kernel; the two-tile kernel's twin is in craft_tick_teach.hip).
 #include "craft_launch.h"
@@ -21,6 +21,21 @@ hipError_t launch_policy_actions(const float* logits, int32_t mode, uint64_t see
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(policy_actions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, logits, mode, seed,
                      gid0, tick, n, actions_out);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void policy_ask_kernel(const float* logits, float threshold, int64_t n,
+                                                          uint8_t* ask_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const LogitRow row = load_logit_row(logits, i);
+  ask_out[i] = (uint8_t)policy_ask(row, threshold);
+}
+
+hipError_t launch_policy_ask(const float* logits, float threshold, int64_t n, uint8_t* ask_out, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(policy_ask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, logits, threshold, n,
+                     ask_out);
   return hipGetLastError();
 }
 

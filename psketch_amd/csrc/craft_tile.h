@@ -59,6 +59,11 @@ __host__ __device__ constexpr int tile_tick_threads(int tile, int tl) { return t
 // MODE_STREAM whose action is the policy head's (craft_policy.h): the slot's 24 bytes of logits
 // are requested where the given action is, in the same batch, and the head's arithmetic runs
 // where the hashed draw does.  kHead is false in every other instantiation, whose code is as before.
+// MODE_LANG_HEAD / MODE_LANG_STREAM_HEAD (craft_step_lang_policy, craft_step_lang_policy_stream)
+// are the language modes with the head.  With a second head (a.alt_logits: the instructed model's
+// row) both rows and the use_alt byte are requested in the one batch; then row, mode and seed are
+// selected per lane by use_alt and the head runs once on the selection: the arithmetic of one
+// head, and the result of running both and choosing.
 template <int WIN, int MODEX, int TILE, int TL = 0, int NW = 0>
 __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? CRAFT_TT_WPE : 1) void tile_kernel(SimView v, TileArgs a) {
   constexpr int MODE = mode_base(MODEX);
@@ -130,13 +135,17 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
     // episode ends, and the fetch of the next queue entry and the row loads behind it then wait
     // for these and the state, not for the inventory and the mask queued after them)
     LogitRow lrow{};                                       // kHead: the slot's logits
+    LogitRow arow{};                                       // kHead && kLang: its alt row (a.alt_logits)
     if (kQueue && live) {
       cur = a.q_cursor[slot];
       if constexpr (kHead) lrow = load_logit_row(a.logits, slot);
       else if (a.actions) act = a.actions[slot];
+      if constexpr (kHead && kLang) {
+        if (a.alt_logits) arow = load_logit_row(a.alt_logits, slot);
+      }
       if (a.bc) {
         bc = a.bc[slot];
-        ref = a.ref[slot];
+        if (!(kHead && kLang) || a.ref) ref = a.ref[slot];
       }
     }
     if (live && MODE != MODE_RESET) {
@@ -149,10 +158,13 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
       if (MODE == MODE_TICK || MODE == MODE_LANG) {
         if constexpr (kHead) lrow = load_logit_row(a.logits, slot);
         else if (a.actions) act = a.actions[slot];
+        if constexpr (kHead && kLang) {
+          if (a.alt_logits) arow = load_logit_row(a.alt_logits, slot);
+        }
         // (MODE_LANG: use_alt and alt_actions, the same two loads in the same batch)
         if (a.bc) {
           bc = a.bc[slot];
-          ref = a.ref[slot];
+          if (!(kHead && kLang) || a.ref) ref = a.ref[slot];
         }
       } else if (MODE == MODE_TRANSITION) {
         act = a.actions[env0 + tid];
@@ -195,7 +207,20 @@ __global__ __launch_bounds__(tile_tick_threads(TILE, TL) + TILE * TL, TL > 0 ? C
           s.x = x0; s.y = y0; s.dir = d0; s.frozen = 0; s.timer = v.maxT; s.scen = sc; s.task = tk;
         }
       } else {
-        if (kTick) {
+        if constexpr (kHead && kLang) {
+          // the selected head: the alt row, mode and seed where use_alt is set and there is a
+          // second head, else the main ones (selects, no branch); one policy_head per lane
+          const bool alt = a.alt_logits && (bc & 0xffu);
+          LogitRow sel;
+          sel.a.x = alt ? arow.a.x : lrow.a.x; sel.a.y = alt ? arow.a.y : lrow.a.y;
+          sel.b.x = alt ? arow.b.x : lrow.b.x; sel.b.y = alt ? arow.b.y : lrow.b.y;
+          sel.c.x = alt ? arow.c.x : lrow.c.x; sel.c.y = alt ? arow.c.y : lrow.c.y;
+          const int32_t hmode = alt ? a.alt_mode : a.head_mode;
+          const uint64_t hseed = alt ? a.alt_seed : a.head_seed;
+          act = policy_head(sel, hmode, hseed, (uint64_t)(v.env_base + slot), a.tick);
+          // no second head: use_alt takes the integer alt_actions as in MODE_LANG
+          if (!a.alt_logits && a.bc && (bc & 0xffu)) act = ref;
+        } else if (kTick) {
           if constexpr (kHead) act = policy_head(lrow, a.head_mode, a.head_seed, (uint64_t)(v.env_base + slot), a.tick);
           else if (!a.actions) act = hashed_action(v, a.seed, slot, a.tick);
           asm volatile("" : "+v"(bc), "+v"(ref));                      // (no early wait on the flag)

@@ -17,13 +17,15 @@ The student is duck-typed after the reference's students, batched (INTEGRATION.m
 signatures); `teacher` is a language.PrimitiveLanguageTeacher, whose student_action_map and
 draws from the shared RandomState come out as the reference's.
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from . import _native as N
 from .language import WORDS
 from .rollout import (EvalContext, EvalInfo, RolloutError, _Info, _LiveFlags,  # noqa: F401
-                      _actions, _distances, _queue_pass)
+                      _actions, _distances, _head_struct, _policy_output, _queue_pass)
 
 MODES = ("primitive", "interactive", "active")
 PAD = "<PAD>"
@@ -56,7 +58,7 @@ class _Pass:
     """One pass of the loop `while not all(done)` from the episodes' initial states: the
     buffers of its ticks and the tick itself."""
 
-    def __init__(self, sim, spec, teach):
+    def __init__(self, sim, spec, teach, head=None, head_seed=0):
         n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
         self.sim, self.n, self.T = sim, n, T
         self.obs = sim.empty_obs()
@@ -75,14 +77,21 @@ class _Pass:
         self.args.obs = self.obs.data_ptr()
         if teach:
             self.args.label_out = self.new_labels.data_ptr()
+        # with a head: `actions` and `alt` are float32 [n, 6] logits, the call craft_step_lang_policy
+        self.head = self.alt_head = None
+        if head is not None:
+            self.head = _head_struct(head, head_seed)
+            self.alt_head = _head_struct(head, alt_seed(head_seed))
 
     def tick(self, actions, alt=None, use_alt=None):
         """One craft_step_lang launch, then the read of its any-live flag: True while some env
         is still running."""
         t, a, sim = self.ticks, self.args, self.sim
+        a.use_alt = None if use_alt is None else use_alt.data_ptr()
+        if self.head is not None:
+            return self._head_tick(actions, alt)
         a.actions = actions.data_ptr()
         a.alt_actions = None if alt is None else alt.data_ptr()
-        a.use_alt = None if use_alt is None else use_alt.data_ptr()
         a.tick = t
         a.action_record = self.seqs[t].data_ptr()
         a.ask_record = self.asks[t].data_ptr()
@@ -93,16 +102,54 @@ class _Pass:
         self.live.record(t)
         return self.live.wait(t)
 
+    def _head_tick(self, logits, alt_logits):
+        t, a, sim = self.ticks, self.args, self.sim
+        self.head.logits = logits.data_ptr()
+        alt = None
+        if alt_logits is not None:
+            self.alt_head.logits = alt_logits.data_ptr()
+            alt = ctypes.byref(self.alt_head)
+        a.tick = t
+        a.action_record = self.seqs[t].data_ptr()
+        a.ask_record = self.asks[t].data_ptr()
+        a.transition_code = self.codes[t].data_ptr()
+        a.any_live = self.live.ptr(t)
+        sim._check(sim._L.craft_step_lang_policy(sim._h, a, ctypes.byref(self.head), alt, sim._stream()),
+                   "craft_step_lang_policy")
+        self.ticks = t + 1
+        self.live.record(t)
+        return self.live.wait(t)
 
-def do_language_rollout(sim, spec, student, teacher, is_eval, mode, ref_actions=None):
+
+def alt_seed(head_seed):
+    """The seed of the instructed model's head in active training: head_seed ^ 1.  The SAMPLE
+    draw hashes seed ^ (global env id << 20) ^ tick with tick < 2^20, so flipping bit 0 of the seed
+    gives the instructed head the uniform number the main head has at tick ^ 1, never the one it has at this tick:
+    the two heads' draws of a tick are distinct hashes."""
+    return (int(head_seed) ^ 1) & (2**64 - 1)
+
+
+def do_language_rollout(sim, spec, student, teacher, is_eval, mode, ref_actions=None, head=None, head_seed=0,
+                        ask_threshold=None):
     """One rollout of sim.n_envs episodes under the protocol of the reference's language
     trainer `mode` ("primitive", "interactive" or "active"); returns a LanguageRolloutInfo.
 
     spec: (scenario, x, y, dir, task), each n_envs ints.  ref_actions (primitive only): each
     env's demonstration, which teacher.instruct turns into its instruction
-    (primitive_language.py:26).  Eager loop: no graph capture, no lookahead."""
+    (primitive_language.py:26).  Eager loop: no graph capture, no lookahead.
+    head: None, "argmax" or "sample".  With a head the student's act / instructed_act return
+      float32 [n, 6] logits instead of actions and the tick chooses each env's action itself
+      (craft_step_lang_policy), as rollout.do_rollout(head=) does.  In active training the main
+      logits go to the head seeded head_seed and the instructed logits to the alt head seeded
+      alt_seed(head_seed) = head_seed ^ 1, both under mode `head`; an env acts on the instructed
+      head where it asked.
+    ask_threshold (active training with a head): the driver computes the ask bits itself,
+      sim.policy_ask(main logits, ask_threshold) (the reference student's entropy / log(6) >
+      threshold), between the two decodes, and student.act returns the logits alone."""
     if mode not in MODES:
         raise ValueError(f"mode {mode!r}: one of {MODES}")
+    if ask_threshold is not None and head is None:
+        raise ValueError("ask_threshold needs a head (the ask rule reads the student's logits)")
     if sim.config.max_timesteps <= 0:
         raise ValueError("max_timesteps must be positive")
     n, dev = sim.n_envs, sim.device
@@ -110,12 +157,12 @@ def do_language_rollout(sim, spec, student, teacher, is_eval, mode, ref_actions=
     task = spec[4].contiguous()
     is_eval = bool(is_eval)
     if mode == "primitive":
-        return _primitive(sim, spec, task, student, teacher, is_eval, ref_actions)
+        return _primitive(sim, spec, task, student, teacher, is_eval, ref_actions, head, head_seed)
     train = not is_eval
     active = mode == "active"
     student.init(n)
     student.set_tasks(task, is_eval)
-    p = _Pass(sim, spec, teach=train)
+    p = _Pass(sim, spec, teach=train, head=head, head_seed=head_seed)
     # the teacher's label of every env's current state; a done env keeps its last one
     labels = None
     raised = torch.zeros((), dtype=torch.bool, device=dev)   # the reference's teacher raised
@@ -130,22 +177,27 @@ def do_language_rollout(sim, spec, student, teacher, is_eval, mode, ref_actions=
         obs = p.obs
         alt = ask = None
         if is_eval:
-            actions = _actions(student.act(obs, t), n, dev)
+            actions = _policy_output(student.act(obs, t), n, dev, head)
         elif active:
-            actions, ask = student.act(obs, t)
-            actions = _actions(actions, n, dev)
+            if ask_threshold is not None:
+                # the main model decodes; the ask bits; the instructions; the instructed model
+                actions = _policy_output(student.act(obs, t), n, dev, head)
+                ask = sim.policy_ask(actions, ask_threshold) * ASK
+            else:
+                actions, ask = student.act(obs, t)
+                actions = _policy_output(actions, n, dev, head)
             ask = (torch.as_tensor(ask, device=dev).reshape(n) == ASK).to(torch.uint8).contiguous()
             asked = ask != 0
             # the teacher is asked about ASK envs only, done ones included (:51-54)
             raised |= ((labels == -2) & asked).any()
             instr = torch.where(asked, labels, instr)
             student.set_instructions(instr)
-            alt = _actions(student.instructed_act(obs, t, ask), n, dev)
+            alt = _policy_output(student.instructed_act(obs, t, ask), n, dev, head)
         else:
             raised |= (labels == -2).any()           # asked about every env, done or not (:49-51)
             instr = labels
             student.set_instructions(instr)
-            actions = _actions(student.instructed_act(obs, t), n, dev)
+            actions = _policy_output(student.instructed_act(obs, t), n, dev, head)
         more = p.tick(actions, alt, ask)
         if train:
             # a slot done before the tick was not labelled (-1): it keeps its last label
@@ -180,7 +232,7 @@ def do_language_rollout(sim, spec, student, teacher, is_eval, mode, ref_actions=
     return _summary(sim, task, p, num_interactions, num_steps, raised)
 
 
-def evaluate(sim, specs, act, ids=None, max_ticks=None):
+def evaluate(sim, specs, act, ids=None, max_ticks=None, head=None, head_seed=0):
     """The reference's evaluate of its three language trainers, one pass over `specs`.  They
     inherit ImitationTrainer.evaluate (trainers/primitive_language.py:14, imitation.py:183-226),
     which loops over THEIR do_rollout(..., is_eval=True); in eval mode the three run the same env
@@ -218,11 +270,15 @@ def evaluate(sim, specs, act, ids=None, max_ticks=None):
             labels = new.clone()                       # every slot runs on: no -1 under wrap
 
     Under wrap no slot freezes, so every label is the teacher's answer for the state the student
-    sees next, a restarted slot's for its new task."""
-    return _queue_pass(sim, specs, act, ids, max_ticks, lang=True)
+    sees next, a restarted slot's for its new task.
+
+    head: None, "argmax" or "sample": act returns float32 [n, 6] logits and the tick chooses the
+    action (craft_step_lang_policy_stream), as rollout.evaluate(head=) does; with logits the loop
+    above calls sim.step_lang_stream(logits=..., alt_logits=..., use_alt=ask, ...)."""
+    return _queue_pass(sim, specs, act, ids, max_ticks, lang=True, head=head, head_seed=head_seed)
 
 
-def _primitive(sim, spec, task, student, teacher, is_eval, ref_actions):
+def _primitive(sim, spec, task, student, teacher, is_eval, ref_actions, head=None, head_seed=0):
     n, dev = sim.n_envs, sim.device
     if ref_actions is None or len(ref_actions) != n:
         raise ValueError("primitive mode needs ref_actions, one action sequence per env")
@@ -239,11 +295,11 @@ def _primitive(sim, spec, task, student, teacher, is_eval, ref_actions):
     raised = torch.zeros((), dtype=torch.bool, device=dev)
 
     def run(instructed):
-        p = _Pass(sim, spec, teach=False)
+        p = _Pass(sim, spec, teach=False, head=head, head_seed=head_seed)
         while True:
             t = p.ticks
             act = student.instructed_act if instructed else student.act
-            more = p.tick(_actions(act(p.obs, t), n, dev))
+            more = p.tick(_policy_output(act(p.obs, t), n, dev, head))
             student.terminate(p.done)
             if not more:
                 return p

@@ -639,7 +639,8 @@ def evaluate(sim, specs, act, ids=None, max_ticks=None, head=None, head_seed=0):
 def _queue_pass(sim, specs, act, ids, max_ticks, lang, head=None, head_seed=0):
     """evaluate()'s pass over the queue under either protocol: craft_step_stream (the imitation
     trainer's), or with `lang` craft_step_lang_stream (the language trainers':
-    language_rollout.evaluate).  The two argument structs name their shared fields alike."""
+    language_rollout.evaluate).  The two argument structs name their shared fields alike.  With a
+    head the tick is craft_step_policy_stream / craft_step_lang_policy_stream."""
     n, dev, T = sim.n_envs, sim.device, sim.config.max_timesteps
     specs = _specs_array(specs)
     ids = list(range(len(specs))) if ids is None else list(ids)
@@ -660,9 +661,8 @@ def _queue_pass(sim, specs, act, ids, max_ticks, lang, head=None, head_seed=0):
     what = "craft_step_lang_stream" if lang else "craft_step_stream"
     hd = None
     if head is not None:
-        if lang:
-            raise ValueError("the language ticks take no policy head")
-        what, hd = "craft_step_policy_stream", _head_struct(head, head_seed)
+        what = "craft_step_lang_policy_stream" if lang else "craft_step_policy_stream"
+        hd = _head_struct(head, head_seed)
     args = N.craft_lang_stream_step_args_t() if lang else N.craft_stream_step_args_t()
     args.step.flags = 0 if lang else N.STEP_AUTORESET
     args.step.obs = obs.data_ptr()
@@ -682,7 +682,12 @@ def _queue_pass(sim, specs, act, ids, max_ticks, lang, head=None, head_seed=0):
         args.step.any_live = live.ptr(t)
         args.episode_end = ended[t].data_ptr()
         args.end_pose = pose[t].data_ptr()
-        st = fn(h, pargs, sim._stream()) if hd is None else fn(h, pargs, ctypes.byref(hd), sim._stream())
+        if hd is None:
+            st = fn(h, pargs, sim._stream())
+        elif lang:                                   # (no alt head: an evaluation has one model)
+            st = fn(h, pargs, ctypes.byref(hd), None, sim._stream())
+        else:
+            st = fn(h, pargs, ctypes.byref(hd), sim._stream())
         if st:
             N.check(st, h, what, L=sim._L)
         # the next call's context, on the device

@@ -415,6 +415,32 @@ class CraftSim:
                     "craft_policy_actions")
         return out
 
+    def policy_ask(self, logits, threshold, out=None):
+        """The ask rule alone (craft_policy_ask): uint8 [N], 1 where the entropy of
+        softmax(logits[i]) over ln 6 exceeds threshold (0 <= threshold <= 1), 0 otherwise and for
+        a row with a NaN or +inf or nothing but -inf.  The active language student's
+        `entropy / log(6) > threshold` (students/active_primitive_language.py:116-119) as one
+        launch, bit-identical on every device."""
+        if out is None:
+            out = torch.empty(self.n_envs, dtype=torch.uint8, device=self.device)
+        self._buf("out", out, torch.uint8, (self.n_envs,))
+        keep = []
+        hd = self._head(keep, logits, N.HEAD_ARGMAX, 0)     # (mode and seed are not read)
+        self._check(self._L.craft_policy_ask(self._h, ctypes.byref(hd), ctypes.c_float(float(threshold)), _ptr(out),
+                                             self._stream()), "craft_policy_ask")
+        return out
+
+    def _lang_heads(self, keep, actions, alt_actions, logits, head, head_seed, alt_logits, alt_head, alt_head_seed):
+        """step_lang / step_lang_stream with logits: (the main head, the alt head or None), as
+        ctypes arguments of craft_step_lang_policy* (which refuses actions beside logits,
+        alt_actions beside alt_logits and alt_logits without use_alt)."""
+        if logits is None:
+            raise ValueError("alt_logits needs logits (the main head)")
+        hd = self._head(keep, logits, head, head_seed)
+        if alt_logits is None:
+            return ctypes.byref(hd), None
+        return ctypes.byref(hd), ctypes.byref(self._head(keep, alt_logits, alt_head, alt_head_seed))
+
     def step(self, actions=None, seed=0, tick=0, autoreset=True, obs=None, reward=None, done=None,
              success=None, ref_actions=None, behavior_clone=None, action_record=None,
              any_live=None, transition_code=None, labels=None, logits=None, head="argmax", head_seed=0):
@@ -465,12 +491,16 @@ class CraftSim:
 
     def step_lang(self, actions=None, seed=0, tick=0, alt_actions=None, use_alt=None, obs=None,
                   done=None, success=None, action_record=None, ask_record=None,
-                  transition_code=None, any_live=None, labels=None, flags=0):
+                  transition_code=None, any_live=None, labels=None, flags=0, logits=None, head="argmax",
+                  head_seed=0, alt_logits=None, alt_head="argmax", alt_head_seed=0):
         """One tick of the language trainers' rollout for every slot (include/craft.h
         craft_step_lang): every running slot steps first (STOP too), then its timer drops and
         done latches; success is satisfies() of the new state.  actions: int32 [N] or None for
         the hashed draw; use_alt (uint8 [N]) picks alt_actions (int32 [N]) per slot, the active
-        trainer's ASK bit.  Outputs, each optional: done uint8, success int8 (-1 running or
+        trainer's ASK bit.  logits (float32 [N, 6]) in place of actions: the tick chooses each
+        slot's action itself (craft_step_lang_policy), head / head_seed as step's; alt_logits
+        in place of alt_actions likewise, under alt_head / alt_head_seed (needs use_alt; seed
+        two "sample" heads apart).  Outputs, each optional: done uint8, success int8 (-1 running or
         None), action_record int32 and ask_record int8 (-1 for a slot done before the tick),
         transition_code int8, any_live int32 [1], labels int32 [N]: the DemonstrationTeacher on
         every new state in the same launch (-1 for a slot done before the tick)."""
@@ -481,6 +511,12 @@ class CraftSim:
         args.action_seed = seed & (2**64 - 1)
         args.tick = int(tick)
         args.flags = int(flags)
+        if logits is not None or alt_logits is not None:
+            hd, alt = self._lang_heads(keep, actions, alt_actions, logits, head, head_seed, alt_logits, alt_head,
+                                       alt_head_seed)
+            self._check(self._L.craft_step_lang_policy(self._h, ctypes.byref(args), hd, alt, self._stream()),
+                        "craft_step_lang_policy")
+            return obs
         self._check(self._L.craft_step_lang(self._h, ctypes.byref(args), self._stream()),
                     "craft_step_lang")
         return obs
@@ -542,8 +578,10 @@ class CraftSim:
     def step_lang_stream(self, actions=None, seed=0, tick=0, alt_actions=None, use_alt=None, obs=None,
                          done=None, success=None, action_record=None, ask_record=None,
                          transition_code=None, any_live=None, labels=None, episode_end=None,
-                         end_pose=None, episode_now=None, flags=0):
-        """step_lang on the episode queue (craft_step_lang_stream): every running slot steps
+                         end_pose=None, episode_now=None, flags=0, logits=None, head="argmax", head_seed=0,
+                         alt_logits=None, alt_head="argmax", alt_head_seed=0):
+        """step_lang on the episode queue (craft_step_lang_stream; with logits
+        craft_step_lang_policy_stream, as step_lang): every running slot steps
         first, the ending tick included, success is satisfies() of the state that step left, and
         a slot whose episode ended then restarts on its next queue entry.  step_lang's arguments
         plus step_stream's three int32 [N] outputs: episode_end, end_pose (the pose AFTER the
@@ -559,6 +597,12 @@ class CraftSim:
         st.tick = int(tick)
         st.flags = int(flags)
         self._queue_outs(args, keep, (n,), episode_end, end_pose, episode_now)
+        if logits is not None or alt_logits is not None:
+            hd, alt = self._lang_heads(keep, actions, alt_actions, logits, head, head_seed, alt_logits, alt_head,
+                                       alt_head_seed)
+            self._check(self._L.craft_step_lang_policy_stream(self._h, ctypes.byref(args), hd, alt, self._stream()),
+                        "craft_step_lang_policy_stream")
+            return obs
         self._check(self._L.craft_step_lang_stream(self._h, ctypes.byref(args), self._stream()),
                     "craft_step_lang_stream")
         return obs
